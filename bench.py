@@ -1,8 +1,12 @@
 """Pi0 training throughput (+ action-chunk inference latency) on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline fields only; the
+other legs' fields are null).  ``--dump-outputs DIR`` writes what the last timed step computed as
+``DIR/<name>.npy``.  ``--full`` adds every other leg listed under "Also reported" below.
 
 Workload (BASELINE.json metric, configs[1]/[2]): bridge-shaped synthetic batch
 (256 image + 20 text + 1 proprio + 4 action tokens), full Pi0 (SigLIP-So400m +
@@ -12,7 +16,7 @@ bnb AdamW8bit) over 2.6B trained parameters.
 One step = one optimizer update at global batch 1024 (= N GPUs x micro-batch x
 accumulation); with N GPUs the grads are all-reduced over RCCL, overlapped
 with the last micro-batch's backward.  ``value`` = samples/s of the whole job.
-Also reported: bf16 action-chunk inference latency (B=1, hipGraph replay),
+Also reported (``--full`` only): bf16 action-chunk inference latency (B=1, hipGraph replay),
 the dominant kernel's roofline (live HIP-event timing of the vlm GeGLU GEMM),
 and the CPU restatement (oracle/) timed on this host.
 """
@@ -278,6 +282,31 @@ def _graph_ms(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
+DUMP_SAMPLE = 1 << 22  # arena elements sampled by --dump-outputs (16 MB of float32 per array)
+
+
+def dump_outputs(path, model, losses, gnorms):
+    """--dump-outputs: what the timed training steps hand their caller, as path/<name>.npy.  The mean micro-batch
+    loss and the pre-clip gradient norm of every step (warm-up steps first, float64), and -- the step's 2.6 B
+    gradients and updated weights being too large to keep whole -- the same DUMP_SAMPLE seeded positions of the
+    gradient arena (the last step's accumulated, unclipped gradients: zero_grad only drops the views) and of the
+    parameter arena after the last update (float32, exact from bf16).  The positions depend on the arena size alone,
+    so two builds are compared element for element."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arena = model._arena
+    idx = torch.randint(0, arena.data.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(20240))
+    idx = idx.sort().values.to(arena.data.device)
+    out = {"loss_per_step": np.asarray(losses, dtype=np.float64),
+           "grad_norm_per_step": np.asarray(gnorms, dtype=np.float64),
+           "grad_sample": arena.ensure_grad()[idx].float().cpu().numpy(),
+           "param_sample": arena.data[idx].float().cpu().numpy()}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[bench] wrote {', '.join(sorted(out))} ({sum(a.nbytes for a in out.values()) / 1e6:.1f} MB) to {path}")
+
+
 def _free_port():
     import socket
 
@@ -394,6 +423,13 @@ def main():
     # measured 260.5 vs 252.5 samples/s for 128 x 8 on one box (profiles/r04/mb256_ab.txt; 247 GB peak of the
     # 288 GB), 128 x 8 255.7 vs 64 x 16 248.0 (profiles/r04/mb_ab.txt).  At 8 GPUs each rank runs 128 x 1.
     ap.add_argument("--micro-batch", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: the dominant kernel's live roofline probe, the action-chunk "
+                         "inference latencies (bridge and Pi0-paper shapes, bf16 and fp8) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed as DIR/<name>.npy (float32 / "
+                         "float64): every step's loss and gradient norm and a fixed seeded sample of the gradients "
+                         "and of the updated parameters")
     ap.add_argument("--infer-iters", type=int, default=100)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-infer", action="store_true")
@@ -403,6 +439,8 @@ def main():
                     help="run the data-parallel path (process group + PiZeroDDP bucketed RCCL all-reduce on the "
                          "comm stream) even at world size 1 (single-GPU check of the N>1 code path)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus is not None and args.gpus > 1:
@@ -488,7 +526,9 @@ def main():
     # live probe of the dominant kernel: the vlm GeGLU gate|up GEMM (M = mb*276, N = 2*16384, K = 2048)
     d = model._engine().d
     Mg, Ng, Kg = mb * d.P, 2 * d.gI, d.gH
-    probe = ops.set_probe(lambda M, N, K, epi, batch: (M, N, K, epi) == (Mg, Ng, Kg, ops.PZ_EPI_GEGLU))
+    probe = []
+    if args.full:
+        probe = ops.set_probe(lambda M, N, K, epi, batch: (M, N, K, epi) == (Mg, Ng, Kg, ops.PZ_EPI_GEGLU))
     if ddp:
         meta.reducer.timing = True  # RCCL time per bucket + the un-hidden wait
         n_log0 = len(meta.reducer.log)
@@ -548,8 +588,11 @@ def main():
     achieved = flops_launch / (kern_ms * 1e-3) / 1e12 if durs else None
     samples_s = gb * args.steps / el
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, losses, gnorms)
+
     infer = None
-    if not args.no_infer and rank == 0:
+    if args.full and not args.no_infer and rank == 0:
         batches = None
         torch.cuda.empty_cache()  # the training step's activation blocks (micro-batch 256: ~240 GB) go back
         model.eval()
@@ -590,11 +633,11 @@ def main():
                  "frac": INFER_BYTES / (graph_ms * 1e-3) / (PEAK_HBM_GBPS * 1e9)}
 
     c5 = None
-    if not args.no_infer and not args.no_c5 and rank == 0:
+    if args.full and not args.no_infer and not args.no_c5 and rank == 0:
         c5 = c5_inference(cfg, dev, args.infer_iters)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0:
@@ -614,7 +657,8 @@ def main():
                 "forced_at_world_1": bool(args.force_ddp and world == 1), "replica_weights_equal": replicas_equal,
                 **(comm or {})},
             "mfma_frac_step": samples_s * TRAIN_FLOP_PER_SAMPLE / (world * PEAK_BF16_TFLOPS * 1e12),
-            "roofline": {"bound": "mfma", "kernel": kname + " (vlm gate|up GeGLU GEMM)",
+            "roofline": None if not args.full else {
+                         "bound": "mfma", "kernel": kname + " (vlm gate|up GeGLU GEMM)",
                          "shape_MNK": [Mg, Ng, Kg], "launches_timed": len(durs), "avg_launch_ms": kern_ms,
                          "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
                          "frac": None if achieved is None else achieved / PEAK_BF16_TFLOPS,

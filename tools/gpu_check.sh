@@ -14,10 +14,10 @@ for s in $STEPS; do
       timeout -k 10 900 python -u -m pytest ${TESTS:-tests} -m gpu -x -v --timeout 300 --timeout-method thread \
         > "$OUT/tests.log" 2>&1 ;;
     bench)
-      timeout -k 10 600 python -u bench.py > "$OUT/bench.log" 2>&1 ;;
+      timeout -k 10 600 python -u bench.py --full > "$OUT/bench.log" 2>&1 ;;
     prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench \
-        -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > "$OUT/prof.log" 2>&1
+        -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > "$OUT/prof.log" 2>&1
       # the full trace (~100 MB) exceeds what gpurun copies back; keep the per-dispatch rows of the
       # dominant GEMM only (grid split / duration check) and the stats summary
       python3 - "$OUT/prof" <<'PY'
