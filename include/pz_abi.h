@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PZ_ABI_VERSION 20
+#define PZ_ABI_VERSION 21
 
 enum {
   PZ_OK = 0,
@@ -414,6 +414,31 @@ int pz_copy_rows(const void* src, int64_t sld, int64_t sbs, void* dst, int64_t d
 /* bf16 <-> fp32 copies / scaled adds */
 int pz_cast_f32_bf16(const float* x, void* y, int64_t n, void* stream);
 int pz_cast_bf16_f32(const void* x, float* y, int64_t n, void* stream);
+
+/* (ABI 21) adaLN / adaLN-Zero action expert (vla/modules.py:78-119, joint_model.py:70-79,117-126): row passes
+ * conditioned on per-sample fp32 modulation rows.  gamma_pre / beta / gate_pre point at column 0 of their slot in
+ * one fp32 [B, ldmod] buffer (cond @ W^T without bias, from pz_gemm with c_fp32); the [D] bf16 biases are added
+ * here.  Sample of a row: b = row / rows_per_sample (rows_per_sample must divide R).  D % 8 == 0, D <= 2048, bf16
+ * rows 16-byte aligned, modulation rows 16-byte aligned (ldmod % 4 == 0).
+ *   stage 1 (y != NULL):  xm = x + y * sigmoid(gate_pre[b] + gate_bias), written to xm (bf16)
+ *   stage 2 (h != NULL):  h = xm * rsqrt(mean(xm^2) + eps) * sigmoid(gamma_pre[b] + gamma_bias) + beta[b];
+ *                         rstd fp32 [R] saved when given (xm = x when stage 1 is off) */
+int pz_adaln_fwd(const void* x, int64_t ldx, const void* y, int64_t ldy, const float* gate_pre,
+                 const void* gate_bias, void* xm, int64_t ldxm, const float* gamma_pre, const void* gamma_bias,
+                 const float* beta, void* h, int64_t ldh, float* rstd, int64_t ldmod, int64_t R, int64_t D,
+                 int64_t rows_per_sample, float eps, void* stream);
+/* dx = dres + d(adaptive norm)/dx . dh (dres may alias dx, may be NULL; its row stride is lddx);
+ * dgamma_pre[b, :] = sigma'(.) * sum_rows dh * xhat and dbeta[b, :] = sum_rows dh, written (not accumulated) into
+ * their fp32 slots, summed in a fixed order without atomics (bitwise repeatable); either may be NULL */
+int pz_adaln_norm_bwd(const void* dh, int64_t lddh, const void* x, int64_t ldx, const float* rstd,
+                      const float* gamma_pre, const void* gamma_bias, const void* dres, void* dx, int64_t lddx,
+                      float* dgamma_pre, float* dbeta, int64_t ldmod, int64_t R, int64_t D, int64_t rows_per_sample,
+                      void* stream);
+/* backward of stage 1's branch: dy = dout * sigma, dgate_pre[b, :] = sigma (1 - sigma) * sum_rows dout * y
+ * (written, fixed order); the residual path takes dout unchanged */
+int pz_adaln_gate_bwd(const void* dout, int64_t lddo, const void* y, int64_t ldy, const float* gate_pre,
+                      const void* gate_bias, void* dy, int64_t lddy, float* dgate_pre, int64_t ldmod, int64_t R,
+                      int64_t D, int64_t rows_per_sample, void* stream);
 
 /* test instrument: fill every CU's LDS with `word` (0xffffffff = NaN) on `stream`, so the next kernel's reads of
  * LDS it did not write return NaN (tests/test_train_loop_gpu.py; _lib.call runs it before every launch under

@@ -19,7 +19,7 @@ if os.environ.get("PZ_LIB_PATH"):
     print(f"[pizero_native] PZ_LIB_PATH override: loading {LIB_PATH} instead of the default libpizero_hip.so",
           file=_sys.stderr, flush=True)
 
-ABI_VERSION = 20  # include/pz_abi.h PZ_ABI_VERSION
+ABI_VERSION = 21  # include/pz_abi.h PZ_ABI_VERSION
 PZ_EPI_NONE, PZ_EPI_GELU, PZ_EPI_GEGLU, PZ_EPI_SILU = 0, 1, 2, 3
 PZ_EPI_DGELU, PZ_EPI_DSILU, PZ_EPI_DGEGLU = 4, 5, 6
 PZ_SUMSQ_PARTS = 2048  # include/pz_abi.h
@@ -178,6 +178,9 @@ SIGNATURES = {
     "pz_fill_uniform": [vp, i32, i64, C.c_uint64, f32, f32, vp],
     "pz_cast_f32_bf16": [vp, vp, i64, vp],
     "pz_cast_bf16_f32": [vp, vp, i64, vp],
+    "pz_adaln_fwd": [vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, f32, vp],
+    "pz_adaln_norm_bwd": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, i64, i64, vp],
+    "pz_adaln_gate_bwd": [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, vp],
     "pz_debug_poison_lds": [C.c_uint32, vp],
     "pz_debug_spin": [i64, i64, vp],
     "pz_last_error": [],

@@ -130,10 +130,21 @@ def region_marks(model):
 
     nL = model.joint_model.num_hidden_layers
     head = ["action_decoder.weight", "action_decoder.bias", "joint_model.mixtures.action.norm.weight"]
+    # adaLN expert: a layer's time-conditioning Linears are not final with that layer -- they sit in the modulation
+    # block after expert layer 0 (pizero.adaln_slots) and their gradients are issued after the joint backward, so only
+    # the ("encoders", -1) mark covers them
+    late = set()
+    ada = getattr(model, "action_expert_adaptive_mode", None)
+    if ada:
+        from src.model.vla.pizero import adaln_slots
+
+        for mix in ("action", "proprio"):
+            sl = adaln_slots(f"joint_model.mixtures.{mix}.", nL, ada)
+            late.update(sl["w"] + sl["b"])
     for l in range(nL):
         e = {}
-        an = [n for n in ar.order if n.startswith(f"joint_model.mixtures.action.layers.{l}.")
-              or n.startswith(f"joint_model.mixtures.proprio.layers.{l}.")]
+        an = [n for n in ar.order if n not in late and (n.startswith(f"joint_model.mixtures.action.layers.{l}.")
+                                                        or n.startswith(f"joint_model.mixtures.proprio.layers.{l}."))]
         vn = [n for n in ar.order if n.startswith(f"joint_model.mixtures.vlm.layers.{l}.")]
         if an:
             e["action"] = max(end_of(an), end_of(head))

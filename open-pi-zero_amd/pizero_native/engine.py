@@ -82,6 +82,8 @@ class Dims:
     clip: float | None
     time_bf16: bool = False  # pz_time_embed mode 1: the reference's bf16 arithmetic (see modules.py)
     n_images: int = 1  # images per sample (C5, the Pi0-paper shape: 3)
+    ada: str | None = None  # action_expert_adaptive_mode: None | "adaLN" | "adaLN-Zero"
+    tH: int = 0  # time_hidden_size: width of the time condition of the adaLN expert
 
     @property
     def img_tok(self):
@@ -118,6 +120,8 @@ class Dims:
             steps=int(_cfg(cfg, "num_inference_steps")), clip=None if clip is None else float(clip),
             time_bf16=bool(_cfg(cfg, "time_embed_bf16_reference", False)),
             n_images=int(_cfg(cfg, "num_images", 1)),
+            ada=_cfg(cfg, "action_expert_adaptive_mode", None) or None,
+            tH=int(_cfg(cfg, "time_hidden_size", 0) or 0),
         )
 
     @property
@@ -178,6 +182,61 @@ def _mask_kw(d, cnt, which):
         m = getattr(cnt, which)
         return dict(mask_mode=2, mask=m, ldm=m.shape[2], mask_bstride=m.shape[1] * m.shape[2])
     return dict(mask_mode=1, cnt=cnt, prefix=d.P, cond=d.C)
+
+
+FP8_ADAPTIVE_MSG = ("fp8 inference is not available with action_expert_adaptive_mode (adaLN / adaLN-Zero): the fp8 "
+                    "norm-to-codes kernels are Gemma-RMSNorm specific and the reference has no fp8 path")
+
+
+class Ada:
+    """Time modulation of one adaLN expert group for one forward / denoise step: ``mod`` fp32 [B, nslots * hidden],
+    every site's gamma_pre / beta / gate_pre rows (cond @ W^T, biases added by the row kernels), from ONE GEMM of
+    the time embedding against the mixture's adjacent conditioning weights (pizero.adaln_slots); ``dmod``: the
+    matching per-sample gradient rows, filled by the backward row kernels."""
+
+    def __init__(self, eng, g, cond):
+        self.eng, self.D, self.zero = eng, g.hid, eng.d.ada == "adaLN-Zero"
+        self.sl = eng.ada_slots(g.prefix[: -len("layers.")])
+        self.W = eng.ar.span(self.sl["w"][0], self.sl["w"][-1])
+        self.mod = torch.empty(cond.shape[0], self.W.shape[0], device=cond.device, dtype=F32)
+        ops.linear(cond, self.W, self.mod)
+        self.dmod = None
+
+    def biased(self, layer, site):
+        """(first column, bias [hidden]) of a to_gamma / layer-scale gate slot"""
+        i = self.sl["slot"][(layer, site)]
+        return i * self.D, self.eng.w(self.sl["b"][i])
+
+    def beta(self, layer, site):
+        return self.sl["slot"][(layer, site)] * self.D
+
+    def norm_fwd(self, x, layer, site, T, h, rstd=None, y=None, gate=None, xm=None):
+        """h = AdaptiveRMSNorm_site(xm), xm = x (+ y * gate); site: "in" | "post" | "" (the final norm)"""
+        ops.adaln_fwd(x, self.mod, T, self.eng.d.rms_eps, y=y, gate=None if y is None else self.biased(layer, gate),
+                      xm=xm, gamma=self.biased(layer, site + "g"), beta=self.beta(layer, site + "b"), h=h, rstd=rstd)
+
+    def norm_bwd(self, dh, x, rstd, layer, site, T, dx, dres=None):
+        return ops.adaln_norm_bwd(dh, x, rstd, self.mod, self.biased(layer, site + "g"), dx, self.dmod,
+                                  self.beta(layer, site + "b"), T, dres=dres)
+
+    def weight_grads(self, cond, ws, beta):
+        """every conditioning weight gradient from one wgrad GEMM of dmod against the time embedding, every bias
+        gradient from one column sum over the biased slots"""
+        eng, w, b = self.eng, self.sl["w"], self.sl["b"]
+        dm = torch.empty(self.dmod.shape, device=self.dmod.device, dtype=BF16)
+        ops.cast_to_bf16(self.dmod, dm)
+        if all(eng.rg(n) for n in w):
+            ops.linear_wgrad(dm, cond, eng.ar.grad_span(w[0], w[-1]), beta=beta)
+        else:
+            for i, n in enumerate(w):
+                if eng.rg(n):
+                    ops.linear_wgrad(dm[:, i * self.D:(i + 1) * self.D], cond, eng.gw(n), beta=beta)
+        if all(eng.rg(n) for n in b):
+            ops.colsum(dm[:, : len(b) * self.D], eng.ar.grad_span(b[0], b[-1]), ws, beta=beta)
+        else:
+            for i, n in enumerate(b):
+                if eng.rg(n):
+                    ops.colsum(dm[:, i * self.D:(i + 1) * self.D], eng.gw(n), ws, beta=beta)
 
 
 class Group:
@@ -251,6 +310,16 @@ class Engine:
         if self.d.nkv != 1:
             raise NotImplementedError("joint attention kernel path assumes MQA (num_key_value_heads=1, bridge.yaml:176)")
 
+    def ada_slots(self, prefix):
+        """pizero.adaln_slots of one mixture, built once per engine (every denoise step asks for it)"""
+        key = ("ada_slots", prefix)
+        sl = self._tables.get(key)
+        if sl is None:
+            from src.model.vla.pizero import adaln_slots
+
+            sl = self._tables[key] = adaln_slots(prefix, self.d.nL, self.d.ada)
+        return sl
+
     def _chk(self, where, **tensors):
         """PZ_CHECK_FINITE: raise on the first non-finite tensor of this stage (no-op otherwise)"""
         if not self.check_finite:
@@ -287,6 +356,8 @@ class Engine:
         current weights; the codes carry the arena's weight version (``weights_version``) and every
         inference entry point re-quantises them when the weights changed since (fp8_refresh)."""
         d = self.d
+        if d.ada:
+            raise NotImplementedError(FP8_ADAPTIVE_MSG)
         self.f8_version = self.weights_version()
         vt = "vision_tower.vision_model.encoder.layers."
         keys = []
@@ -723,6 +794,19 @@ class Engine:
         rows = psi_bf.shape[0]
         B = t.shape[0]
         dev = psi_bf.device
+        if d.ada:  # time_cond=False (vla/modules.py:33-34,46): no time concat, linear_2 is width -> width
+            e1 = torch.empty(rows, d.aH, device=dev, dtype=BF16)
+            ops.small_linear(psi_bf, self.w("action_encoder.linear_1.weight"), e1,
+                             bias=self.w("action_encoder.linear_1.bias"))
+            pre = None if save is None else torch.empty(rows, d.aH, device=dev, dtype=BF16)
+            e2 = torch.empty(rows, d.aH, device=dev, dtype=BF16)
+            ops.linear(e1, self.w("action_encoder.linear_2.weight"), e2, bias=self.w("action_encoder.linear_2.bias"),
+                       epi=PZ_EPI_SILU, aux=pre)
+            e3 = torch.empty(rows, d.aH, device=dev, dtype=BF16)
+            ops.linear(e2, self.w("action_encoder.linear_3.weight"), e3, bias=self.w("action_encoder.linear_3.bias"))
+            if save is not None:
+                save.update(ae_psi=psi_bf, ae_cat=e1, ae_pre=pre, ae_e2=e2)
+            return e3
         if save is None:
             cat = torch.empty(rows, 2 * d.aH, device=dev, dtype=BF16)
             ops.small_linear(psi_bf, self.w("action_encoder.linear_1.weight"), cat[:, d.aH:],
@@ -785,7 +869,7 @@ class Engine:
         self._jkv_holder = weakref.ref(tok)
         return kv
 
-    def _pre_attn_train(self, g, l, X, pos, st, Qj, Kj, Vj, dev):
+    def _pre_attn_train(self, g, l, X, pos, st, Qj, Kj, Vj, dev, ada=None):
         """One group's input RMSNorm + q|k|v projection + RoPE + joint Q / K / V scatter of joint layer l
         (paligemma/modules.py:7-21, mixture.py:162-215, joint_model.py:170-257)."""
         d = self.d
@@ -796,7 +880,11 @@ class Engine:
         M = x.shape[0]
         h = torch.empty_like(x)
         r = torch.empty(M, device=dev, dtype=F32)
-        ops.rmsnorm(x, self.w(p + "input_layernorm.weight"), h, r, d.rms_eps)
+        A = ada.get(g.name) if ada else None
+        if A is not None:
+            A.norm_fwd(x, l, "in_", g.T, h, r)
+        else:
+            ops.rmsnorm(x, self.w(p + "input_layernorm.weight"), h, r, d.rms_eps)
         # q|k|v projection + RoPE + joint scatter: one 8-phase GEMM whose epilogue rotates and writes
         # Q / K / V (N1: no [M, 2560] qkv tensor, no split launch); rows too few for the 8-phase
         # kernel (the action expert's 320) take GEMM + qkv_rope_split (same bits)
@@ -808,6 +896,40 @@ class Engine:
             ops.qkv_rope_split(qkv, pos[g.pos_key], self.rope(g.theta), Qj, Kj, Vj, B, g.T, nh, 1, hd, L,
                                g.off, Lp, g.off)
         st["g"][g.name] = {"x": x, "h": h, "r": r}
+
+    def _post_attn_ada(self, A, g, l, X, gs, Os, dev, keep=True):
+        """_post_attn_train of an adaLN group: AdaptiveRMSNorm after the attention; adaLN-Zero gates both branch
+        outputs before their residual adds (joint_model.py:70-79,117-126), each in the row pass that follows it:
+        o_proj's with the post-attention norm, the MLP's alone.  keep False (inference): no saved pre-activation."""
+        d = self.d
+        p = f"{g.prefix}{l}."
+        x = X[g.name]
+        M = x.shape[0]
+        O = Os[g.name]
+        xm = torch.empty_like(x)
+        h2 = torch.empty_like(x)
+        r2 = torch.empty(M, device=dev, dtype=F32) if keep else None
+        yo = yd = None
+        if A.zero:
+            yo = torch.empty_like(x)
+            ops.linear(O, self.w(p + "self_attn.o_proj.weight"), yo)
+            A.norm_fwd(x, l, "post_", g.T, h2, r2, y=yo, gate="post_z", xm=xm)
+        else:
+            ops.linear(O, self.w(p + "self_attn.o_proj.weight"), xm, resid=x)
+            A.norm_fwd(xm, l, "post_", g.T, h2, r2)
+        gu = torch.empty(M, 2 * g.inter, device=dev, dtype=BF16) if keep else None
+        hm = torch.empty(M, g.inter, device=dev, dtype=BF16)
+        ops.linear(h2, self.gu_w(p), hm, epi=PZ_EPI_GEGLU, aux=gu)
+        xn = torch.empty_like(x)
+        if A.zero:
+            yd = torch.empty_like(x)
+            ops.linear(hm, self.w(p + "mlp.down_proj.weight"), yd)
+            ops.adaln_fwd(xm, A.mod, g.T, d.rms_eps, y=yd, gate=A.biased(l, "final_z"), xm=xn)
+        else:
+            ops.linear(hm, self.w(p + "mlp.down_proj.weight"), xn, resid=xm)
+        if keep:
+            gs.update(O=O, xm=xm, h2=h2, r2=r2, gu=gu, hm=hm, yo=yo, yd=yd, skip=False)
+        X[g.name] = xn
 
     def _post_attn_train(self, g, l, X, gs, Os, dev):
         """One group's o_proj (+ residual), post-attention RMSNorm and GeGLU MLP (+ residual) of joint layer l
@@ -838,6 +960,7 @@ class Engine:
         S = None
         layers = []
         Kall, Vall = self._joint_kv(B, Lp, dev, save)
+        ada = save.get("ada")
         # the action-expert group's pre- and post-attention work on the second stream, concurrent with the vlm
         # group's; the streams meet at the joint attention (as in _joint_layers_backward)
         main = torch.cuda.current_stream(dev)
@@ -848,6 +971,8 @@ class Engine:
             for t in X.values():
                 if t is not None:
                     t.record_stream(side)
+            for A in (ada or {}).values():
+                A.mod.record_stream(side)
         for l in range(d.nL):
             last = l == d.nL - 1
             Qj = torch.empty(B, L, nh * hd, device=dev, dtype=BF16)
@@ -857,7 +982,7 @@ class Engine:
             st = {"Q": Qj, "K": Kj, "V": Vj, "g": {}}
             for g in groups:
                 with self._on(side, g):
-                    self._pre_attn_train(g, l, X, pos, st, Qj, Kj, Vj, dev)
+                    self._pre_attn_train(g, l, X, pos, st, Qj, Kj, Vj, dev, ada)
             if side is not None:
                 main.wait_stream(side)  # every group's Q / K / V rows before the joint attention
             Os = {g.name: torch.empty(B * g.T, nh * hd, device=dev, dtype=BF16) for g in groups}
@@ -903,7 +1028,10 @@ class Engine:
                     gs["skip"] = True
                     continue
                 with self._on(side, g):
-                    self._post_attn_train(g, l, X, gs, Os, dev)
+                    if ada and g.name in ada:
+                        self._post_attn_ada(ada[g.name], g, l, X, gs, Os, dev)
+                    else:
+                        self._post_attn_train(g, l, X, gs, Os, dev)
             layers.append(st)
             self._chk(f"joint fwd layer {l}", Q=Qj, K=Kj, V=Vj, O=Os, P=st.get("P"), tc=st.get("tc"), X=X)
         if side is not None:  # the expert output and its saved activations are read on the main stream later
@@ -920,13 +1048,18 @@ class Engine:
         save["joint"] = layers
         return X
 
-    def _mlp_oproj_backward(self, g, gs, p, dX, dO, dXm, beta, rpp, nh, hd, dev):
+    def _mlp_oproj_backward(self, g, gs, p, dX, dO, dXm, beta, rpp, nh, hd, dev, A=None, l=None):
         """One group's GeGLU MLP + post-attention RMSNorm + o_proj backward of a joint layer
         (paligemma/modules.py:86-95, mixture.py:216-242): dX[g] -> dO[g] (the attention output gradient)
         and dXm[g] (the residual gradient into the input RMSNorm backward)."""
-        dx = dX[g.name]
+        dx = dres = dX[g.name]
         M = dx.shape[0]
-        part = torch.empty((M + rpp - 1) // rpp, g.hid, device=dev, dtype=F32)
+        part = None if A is not None else torch.empty((M + rpp - 1) // rpp, g.hid, device=dev, dtype=F32)
+        if A is not None and A.zero:
+            # adaLN-Zero: the MLP branch was gated before its residual add -- the branch gradient is dx * sigma (and the
+            # sample's gate gradient), the residual path keeps dx
+            dx = ops.adaln_gate_bwd(dres, gs["yd"], A.mod, A.biased(l, "final_z"), torch.empty_like(dres), A.dmod, g.T)
+            gs["yd"] = None
         # MLP
         # dgrad through down_proj with the GeGLU derivative fused into its epilogue:
         # gu (saved g|u) <- d(gate|up) in place; hm (saved GeGLU output) feeds the down_proj wgrad
@@ -947,18 +1080,25 @@ class Engine:
         dh2 = torch.empty(M, g.hid, device=dev, dtype=BF16)
         ops.linear_dgrad(gu, self.gu_w(p), dh2)
         dxm = torch.empty_like(dx)
-        ops.rmsnorm_bwd(dh2, gs["xm"], self.w(p + "post_attention_layernorm.weight"), gs["r2"], dxm, dres=dx,
-                        dw_part=part)
-        self._norm_grads(p + "post_attention_layernorm.", part, None, beta)
-        # o_proj
+        if A is not None:
+            A.norm_bwd(dh2, gs["xm"], gs["r2"], l, "post_", g.T, dxm, dres=dres)
+        else:
+            ops.rmsnorm_bwd(dh2, gs["xm"], self.w(p + "post_attention_layernorm.weight"), gs["r2"], dxm, dres=dx,
+                            dw_part=part)
+            self._norm_grads(p + "post_attention_layernorm.", part, None, beta)
+        # o_proj (adaLN-Zero: its output was gated before the residual add)
+        dyo = dxm
+        if A is not None and A.zero:
+            dyo = ops.adaln_gate_bwd(dxm, gs["yo"], A.mod, A.biased(l, "post_z"), torch.empty_like(dxm), A.dmod, g.T)
+            gs["yo"] = None
         if self.rg(p + "self_attn.o_proj.weight"):
-            ops.linear_wgrad(dxm, gs["O"], self.gw(p + "self_attn.o_proj.weight"), beta=beta)
+            ops.linear_wgrad(dyo, gs["O"], self.gw(p + "self_attn.o_proj.weight"), beta=beta)
         o = torch.empty(M, nh * hd, device=dev, dtype=BF16)
-        ops.linear_dgrad(dxm, self.w(p + "self_attn.o_proj.weight"), o)
+        ops.linear_dgrad(dyo, self.w(p + "self_attn.o_proj.weight"), o)
         dO[g.name] = o
         dXm[g.name] = dxm
 
-    def _qkv_backward(self, g, gs, p, dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta, rpp, nh, hd, dev):
+    def _qkv_backward(self, g, gs, p, dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta, rpp, nh, hd, dev, A=None, l=None):
         """One group's q|k|v projection + input RMSNorm backward of a joint layer (mixture.py:162-215,
         joint_model.py:170-257 + inverse RoPE): dQ / dK / dV rows of the group -> dX[g]."""
         x = gs["x"]
@@ -992,11 +1132,14 @@ class Engine:
                         ops.linear_wgrad(dqkv[:, c0:c1], gs["h"], self.gw(n), beta=beta)
             dh = torch.empty(M, g.hid, device=dev, dtype=BF16)
             ops.linear_dgrad(dqkv, self.qkv_w(p), dh)
-        part = torch.empty((M + rpp - 1) // rpp, g.hid, device=dev, dtype=F32)
         dxn = torch.empty(M, g.hid, device=dev, dtype=BF16)
-        ops.rmsnorm_bwd(dh, x, self.w(p + "input_layernorm.weight"), gs["r"], dxn, dres=dXm.get(g.name),
-                        dw_part=part)
-        self._norm_grads(p + "input_layernorm.", part, None, beta)
+        if A is not None:
+            A.norm_bwd(dh, x, gs["r"], l, "in_", g.T, dxn, dres=dXm.get(g.name))
+        else:
+            part = torch.empty((M + rpp - 1) // rpp, g.hid, device=dev, dtype=F32)
+            ops.rmsnorm_bwd(dh, x, self.w(p + "input_layernorm.weight"), gs["r"], dxn, dres=dXm.get(g.name),
+                            dw_part=part)
+            self._norm_grads(p + "input_layernorm.", part, None, beta)
         dX[g.name] = dxn
 
     def _joint_layers_backward(self, groups, dX, pos, cnt, B, sv, beta):
@@ -1023,6 +1166,10 @@ class Engine:
             for t in dX.values():
                 if t is not None:
                     t.record_stream(side)
+            for A in (sv.get("ada") or {}).values():
+                A.mod.record_stream(side)
+                A.dmod.record_stream(side)
+        ada = sv.get("ada") or {}
         for l in reversed(range(d.nL)):
             st = sv["joint"][l]
             dQ = torch.empty(B, L, nh * hd, device=dev, dtype=BF16)
@@ -1038,7 +1185,7 @@ class Engine:
                     any_skip = True
                     continue
                 with self._on(side, g):
-                    self._mlp_oproj_backward(g, gs, p, dX, dO, dXm, beta, rpp, nh, hd, dev)
+                    self._mlp_oproj_backward(g, gs, p, dX, dO, dXm, beta, rpp, nh, hd, dev, ada.get(g.name), l)
                 if side is not None and g.name != "vlm":
                     dO[g.name].record_stream(main)
             if side is not None:
@@ -1101,7 +1248,7 @@ class Engine:
             for g in groups:
                 with self._on(side, g):
                     self._qkv_backward(g, st["g"][g.name], f"{g.prefix}{l}.", dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta,
-                                       rpp, nh, hd, dev)
+                                       rpp, nh, hd, dev, ada.get(g.name), l)
             # the layer's expert gradients were produced on the side stream: the reducer's communication stream waits
             # for both streams before it reads them (the compute streams keep running; no main <- side join per layer)
             self._chk(f"joint bwd layer {l}", dO=dO, dS=dS, dQ=dQ, dK=dK, dV=dV, dX=dX)
@@ -1144,6 +1291,13 @@ class Engine:
             ops.copy_rows(e3, d.aH, 0, Xa, d.aH, 0, 1, B * d.H, d.aH, scale=sa)
             X = {"vlm": Xv, "proprio": Xp, "action": Xa}
         groups = self.groups(tied)
+        if d.ada:
+            # the time condition (pizero.py:634; no parameters, t is data: no gradient flows into it) and every
+            # adaLN site's modulation rows of the step, one GEMM per expert group
+            cond = torch.empty(B, d.tH, device=dev, dtype=BF16)
+            ops.time_embed(t, cond, d.tmax, ref_bf16=d.time_bf16)
+            save["cond"] = cond
+            save["ada"] = {g.name: Ada(self, g, cond) for g in groups if g.name != "vlm"}
         X = self._joint_layers_train(groups, X, pos, cnt, B, save)
         ag = "expert" if tied else "action"
         aoff = d.C if tied else 0
@@ -1151,7 +1305,10 @@ class Engine:
         Xl = X[ag]
         ya = torch.empty_like(Xl)
         ra = torch.empty(Xl.shape[0], device=dev, dtype=F32)
-        ops.rmsnorm(Xl, self.w("joint_model.mixtures.action.norm.weight"), ya, ra, d.rms_eps)
+        if d.ada:
+            save["ada"][ag].norm_fwd(Xl, "norm", "", Tg, ya, ra)
+        else:
+            ops.rmsnorm(Xl, self.w("joint_model.mixtures.action.norm.weight"), ya, ra, d.rms_eps)
         v = torch.empty(B * Tg, 8, device=dev, dtype=BF16)  # columns 0..A-1 written and read (8: 16-B rows)
         ops.small_linear(ya, self.w("action_decoder.weight"), v, bias=self.w("action_decoder.bias"))
         loss = torch.empty(1, device=dev, dtype=F32)
@@ -1181,14 +1338,26 @@ class Engine:
         dya = torch.empty(R, d.aH, device=dev, dtype=BF16)
         ops.small_gemm(R, d.aH, d.A, dv, 8, 1, self.w("action_decoder.weight"), d.aH, 1, dya, d.aH)
         dXl = torch.empty_like(dya)
-        part = torch.empty((R + rpp - 1) // rpp, d.aH, device=dev, dtype=F32)
-        ops.rmsnorm_bwd(dya, sv["Xl"], self.w("joint_model.mixtures.action.norm.weight"), sv["ra"], dXl, dw_part=part)
-        self._norm_grads("joint_model.mixtures.action.norm.", part, None, beta)
+        ada = sv.get("ada")
+        if ada:
+            for A in ada.values():  # sites that feed nothing (an untied proprio's last layer and final norm) stay 0
+                A.dmod = torch.zeros_like(A.mod)
+            ada[sv["ag"]].norm_bwd(dya, sv["Xl"], sv["ra"], "norm", "", Tg, dXl)
+        else:
+            part = torch.empty((R + rpp - 1) // rpp, d.aH, device=dev, dtype=F32)
+            ops.rmsnorm_bwd(dya, sv["Xl"], self.w("joint_model.mixtures.action.norm.weight"), sv["ra"], dXl,
+                            dw_part=part)
+            self._norm_grads("joint_model.mixtures.action.norm.", part, None, beta)
         self._chk("train bwd head", dv=dv, dya=dya, dXl=dXl)
         groups = sv["groups"]
         dX = {g.name: None for g in groups}
         dX[sv["ag"]] = dXl
         dX = self._joint_layers_backward(groups, dX, sv["pos"], sv["cnt"], B, sv, beta)
+        if ada:
+            # the expert's layer-0 backward is complete: every conditioning Linear's gradient (the arena block that
+            # follows the expert layers) before the encoders' notification
+            for A in ada.values():
+                A.weight_grads(sv["cond"], self.colsum_ws(A.mod.shape[1]), beta)
         # expert embeddings (joint_model.py:355 scale) -> encoders
         sa = math.sqrt(d.aH)
         dpe = torch.empty(B * d.C, d.aH, device=dev, dtype=BF16)
@@ -1217,10 +1386,14 @@ class Engine:
             ops.linear_wgrad(de2, sv["ae_cat"], self.gw(ae + "linear_2.weight"), beta=beta)
         if self.rg(ae + "linear_2.bias"):
             ops.colsum(de2, self.gw(ae + "linear_2.bias"), ws, beta=beta)
-        dcat = torch.empty(B * d.H, 2 * d.aH, device=dev, dtype=BF16)
-        ops.linear_dgrad(de2, self.w(ae + "linear_2.weight"), dcat)
-        de1 = torch.empty_like(de3)
-        ops.split_time_grad(dcat, de1, B * d.H, d.aH)
+        if d.ada:  # no time concat: linear_2's input gradient is linear_1's output gradient
+            de1 = torch.empty_like(de3)
+            ops.linear_dgrad(de2, self.w(ae + "linear_2.weight"), de1)
+        else:
+            dcat = torch.empty(B * d.H, 2 * d.aH, device=dev, dtype=BF16)
+            ops.linear_dgrad(de2, self.w(ae + "linear_2.weight"), dcat)
+            de1 = torch.empty_like(de3)
+            ops.split_time_grad(dcat, de1, B * d.H, d.aH)
         if self.rg(ae + "linear_1.weight"):
             ops.small_gemm(d.aH, d.A, B * d.H, de1, 1, d.aH, sv["ae_psi"], d.A, 1, self.gw(ae + "linear_1.weight"), d.A,
                            beta=beta)
@@ -1251,6 +1424,8 @@ class Engine:
         dev = Ev.device
         if not self.m._tied:
             raise NotImplementedError("joint_train expects tie_action_proprio_weights() (pizero.py:262-264)")
+        if d.ada:
+            raise NotImplementedError("joint_train takes no time condition: run the adaLN expert through PiZero.forward")
         Xv = torch.empty(B * d.P, d.gH, device=dev, dtype=BF16)
         ops.copy_rows(Ev.reshape(B * d.P, d.gH), d.gH, 0, Xv, d.gH, 0, 1, B * d.P, d.gH, scale=math.sqrt(d.gH))
         T = d.C + d.H
@@ -1308,25 +1483,35 @@ class Engine:
         """few-row GEMV kernels (pz_gemv.hip): M <= 8 rows, K % 512 == 0 (PZ_GEMV=0 disables)"""
         return M <= 8 and K % 512 == 0 and os.environ.get("PZ_GEMV", "1") != "0"
 
-    def prefill(self, ids, pix, cnt, vpos, ppos, proprios, kcache, vcache):
-        """pizero.py:430-451: SigLIP + prefix pass over {vlm, proprio}; writes post-RoPE K/V caches."""
+    def _proprio_rows(self, proprios, B, dev):
+        """proprio encoder output times sqrt(hidden) (pizero.py:100, joint_model.py:355): [B*C, aH] bf16"""
         d = self.d
-        dev = pix.device
-        B = ids.shape[0]
-        nh, hd, Lp = d.nh, d.hd, d.Lp
-        L1 = d.P + d.C
-        img = self.siglip_forward(pix, None)
-        Xv = self.embed_prefix(ids, img)
         prop = proprios.reshape(B * d.C, d.Pd).to(BF16)
         pe = torch.empty(B * d.C, d.aH, device=dev, dtype=BF16)
         ops.small_linear(prop, self.w("proprio_encoder.weight"), pe, bias=self.w("proprio_encoder.bias"))
         Xp = torch.empty(B * d.C, d.aH, device=dev, dtype=BF16)
         ops.copy_rows(pe, d.aH, 0, Xp, d.aH, 0, 1, B * d.C, d.aH, scale=math.sqrt(d.aH))
+        return Xp
+
+    def prefill(self, ids, pix, cnt, vpos, ppos, proprios, kcache, vcache, with_proprio=True):
+        """pizero.py:430-451: SigLIP + prefix pass over {vlm, proprio}; writes post-RoPE K/V caches.
+        with_proprio False (the adaLN expert, whose proprio rows depend on t): the vlm mixture alone -- its rows
+        attend only to vlm rows, so their K/V need neither t nor proprio."""
+        d = self.d
+        dev = pix.device
+        B = ids.shape[0]
+        nh, hd, Lp = d.nh, d.hd, d.Lp
+        L1 = d.P + (d.C if with_proprio else 0)
+        img = self.siglip_forward(pix, None)
+        Xv = self.embed_prefix(ids, img)
+        Xp = None
+        if with_proprio:
+            Xp = self._proprio_rows(proprios, B, dev)
         tied = self.m._tied
         pprefix = "joint_model.mixtures." + ("action" if tied else "proprio") + ".layers."
         groups = [Group("vlm", "joint_model.mixtures.vlm.layers.", ["vlm"], d.P, 0, d.gH, d.gI, d.g_theta, True, "vlm"),
                   Group("proprio", pprefix, ["proprio"], d.C, d.P, d.aH, d.aI, d.p_theta if not tied else d.a_theta,
-                        True, "proprio")]
+                        True, "proprio")][: 2 if with_proprio else 1]
         X = {"vlm": Xv, "proprio": Xp}
         pos = {"vlm": vpos, "proprio": ppos}
         Q = torch.empty(B, L1, nh * hd, device=dev, dtype=BF16)
@@ -1612,10 +1797,105 @@ class Engine:
         ops.small_linear(y, self.w("action_decoder.weight"), v[:, : d.A], bias=self.w("action_decoder.bias"))
         ops.euler_step(action, v, 8, d.H * 8, t, B, d.H, d.A, 1.0 / d.steps)
 
+    def denoise_step_ada(self, action, t, Xp, pos, cnt, kcache, vcache, B):
+        """One Euler step of the adaLN expert with the semantics of the reference's infer_action_naive
+        (pizero.py:492-557): the proprio AND action rows of every sample run again with cond(t) -- the proprio K/V
+        depend on t, so only the vlm K/V are cached -- under the block mask (proprio -> vlm + proprio, action ->
+        all).  Unfused sites: adaptive norm launches, plain q|k|v GEMM + RoPE split, the flash kernel with the query
+        rows starting at token P (or GEMM + softmax), the adaptive final norm + decoder + Euler tail."""
+        d = self.d
+        dev = action.device
+        nh, hd, Lp, L = d.nh, d.hd, d.Lp, d.L
+        tied = self.m._tied
+        T = d.C + d.H
+        cond = torch.empty(B, d.tH, device=dev, dtype=BF16)
+        ops.time_embed(t, cond, d.tmax, ref_bf16=d.time_bf16)
+        groups = self.groups(tied, active=("proprio", "action"))
+        ada = {g.name: Ada(self, g, cond) for g in groups}
+        psi = torch.empty(B * d.H, d.A, device=dev, dtype=BF16)
+        ops.cast_to_bf16(action, psi)
+        e3 = self.action_embed(psi, t, None)
+        sa = math.sqrt(d.aH)
+        if tied:
+            Xe = torch.empty(B * T, d.aH, device=dev, dtype=BF16)
+            ops.copy_rows(Xp, d.aH, d.C * d.aH, Xe, d.aH, T * d.aH, B, d.C, d.aH)
+            ops.copy_rows(e3, d.aH, d.H * d.aH, Xe[d.C:], d.aH, T * d.aH, B, d.H, d.aH, scale=sa)
+            X = {"expert": Xe}
+        else:
+            Xa = torch.empty(B * d.H, d.aH, device=dev, dtype=BF16)
+            ops.copy_rows(e3, d.aH, 0, Xa, d.aH, 0, 1, B * d.H, d.aH, scale=sa)
+            X = {"proprio": Xp, "action": Xa}
+        Q = torch.empty(B, T, nh * hd, device=dev, dtype=BF16)
+        S = Pm = None
+        flash = self.infer_flash and not isinstance(cnt, GeneralMask)
+        for l in range(d.nL):
+            last = l == d.nL - 1
+            Kj, Vj = kcache[l], vcache[l]
+            for g in groups:
+                p = f"{g.prefix}{l}."
+                x = X[g.name]
+                h = torch.empty_like(x)
+                ada[g.name].norm_fwd(x, l, "in_", g.T, h)
+                qkv = torch.empty(x.shape[0], (nh + 2) * hd, device=dev, dtype=BF16)
+                ops.linear(h, self.qkv_w(p), qkv)
+                ops.qkv_rope_split(qkv, pos[g.pos_key], self.rope(g.theta), Q, Kj, Vj, B, g.T, nh, 1, hd, T, g.off - d.P,
+                                   Lp, g.off)
+            # (an untied proprio mixture's last-layer output feeds nothing: computed with the rest -- every query row
+            # belongs to an output group -- and dropped)
+            live = [g for g in groups if not (last and g.skip_last)]
+            Os = {g.name: torch.empty(B * g.T, nh * hd, device=dev, dtype=BF16) for g in groups}
+            if flash:
+                ops.flash_fwd(self._attn_flash_infer(Q, Kj, Vj, [(g.off, g.T, Os[g.name]) for g in groups], T, L, d.P,
+                                                     cnt, B))
+            else:
+                if S is None:
+                    S = torch.empty(B, T * nh, Lp, device=dev, dtype=F32)
+                    Pm = torch.empty(B, T * nh, Lp, device=dev, dtype=BF16)
+                ops.gemm(T * nh, L, hd, Q, hd, True, Kj, hd, True, S, Lp, batch=B, sA=(T * nh * hd, 0),
+                         sB=(Lp * hd, 0), sC=(T * nh * Lp, 0))
+                ops.attn_softmax(S, Lp, Pm, Lp, B * T * nh, L, 1.0 / math.sqrt(hd), cap=50.0, rows_per_batch=T * nh,
+                                 heads=nh, qoff=d.P, **_mask_kw(d, cnt, "act"))
+                for g in live:
+                    ops.gemm(g.T * nh, hd, Lp, Pm[:, (g.off - d.P) * nh:], Lp, True, Vj, hd, False, Os[g.name], hd,
+                             batch=B, sA=(T * nh * Lp, 0), sB=(Lp * hd, 0), sC=(g.T * nh * hd, 0))
+            for g in live:
+                self._post_attn_ada(ada[g.name], g, l, X, None, Os, dev, keep=False)
+        ag = "expert" if tied else "action"
+        Tg, aoff = (T, d.C) if tied else (d.H, 0)
+        y = torch.empty_like(X[ag])
+        ada[ag].norm_fwd(X[ag], "norm", "", Tg, y)
+        v = torch.empty(B * Tg, 8, device=dev, dtype=BF16)
+        ops.small_linear(y, self.w("action_decoder.weight"), v[:, : d.A], bias=self.w("action_decoder.bias"))
+        ops.euler_step(action, v[aoff:], 8, Tg * 8, t, B, d.H, d.A, 1.0 / d.steps)
+
     def infer_action(self, ids, pix, cnt, vpos, ppos, apos, proprios, noise, kcache, vcache, clip=True):
+        """pizero.py:416-490.  With an adaLN expert both this and PiZero.infer_action_naive compute the naive
+        semantics (pizero.py:492-557): the reference's cached infer_action raises AttributeError there ('NoneType'
+        object has no attribute 'ndim' -- its prefill runs the proprio mixture without the time condition), and
+        cannot work, since the proprio K/V depend on t."""
         d = self.d
         B = ids.shape[0]
         self.fp8_refresh()
+        if d.ada:
+            dev = pix.device
+            self.prefill(ids, pix, cnt, vpos, None, None, kcache, vcache, with_proprio=False)
+            Xp = self._proprio_rows(proprios, B, dev)
+            if self.m._tied:
+                pos = {"expert": torch.cat([ppos, apos], dim=1).contiguous()}
+            else:
+                pos = {"proprio": ppos, "action": apos}
+            if isinstance(cnt, GeneralMask):  # rows P.. of the caller's mask: [B, C + H, L] fp32
+                m = torch.full((B, d.C + d.H, d.L), torch.finfo(F32).min, device=dev, dtype=F32)
+                m[:, : d.C, : d.P + d.C] = cnt.itp[:, d.P:, :]
+                m[:, d.C:, :] = cnt.act
+                cnt = GeneralMask(itp=cnt.itp, act=m)
+            action = noise.clone()
+            t = torch.zeros(B, device=dev, dtype=F32)
+            for _ in range(d.steps):
+                self.denoise_step_ada(action, t, Xp, pos, cnt, kcache, vcache, B)
+            if clip and d.clip is not None:
+                ops.clamp_(action, -d.clip, d.clip)
+            return action
         self.prefill(ids, pix, cnt, vpos, ppos, proprios, kcache, vcache)
         action = noise.clone()
         t = torch.zeros(B, device=pix.device, dtype=F32)

@@ -340,6 +340,39 @@ def layernorm_bwd(dy, x, w, mean, rstd, dx, dres=None, dw_part=None, db_part=Non
     return dx
 
 
+def adaln_fwd(x, mod, rows_per_sample, eps, *, y=None, gate=None, xm=None, gamma=None, beta=None, h=None, rstd=None):
+    """adaLN row pass (pz_adaln_fwd).  mod: fp32 [B, N] modulation rows; gate / gamma / beta: that slot's first
+    column in mod; gate = (column, bias [D]) with y, xm: xm = x + y * sigmoid(mod[b, gate] + bias);
+    gamma = (column, bias [D]) with beta, h: h = norm(xm) * sigmoid(mod[b, gamma] + bias) + mod[b, beta]."""
+    R, D = x.shape
+    gp = gb = gmp = gmb = bp = None
+    if y is not None:
+        gp, gb = mod[:, gate[0]:].data_ptr(), _p(gate[1])
+    if h is not None:
+        gmp, gmb, bp = mod[:, gamma[0]:].data_ptr(), _p(gamma[1]), mod[:, beta:].data_ptr()
+    call("pz_adaln_fwd", _p(x), x.stride(0), _p(y), 0 if y is None else y.stride(0), gp, gb, _p(xm),
+         0 if xm is None else xm.stride(0), gmp, gmb, bp, _p(h), 0 if h is None else h.stride(0), _p(rstd),
+         mod.stride(0), R, D, int(rows_per_sample), float(eps), _st())
+
+
+def adaln_norm_bwd(dh, x, rstd, mod, gamma, dx, dmod, beta, rows_per_sample, dres=None):
+    """backward of the adaptive norm: dx = dres + ...; dmod[b, gamma[0]:+D] and dmod[b, beta:+D] (fp32 [B, N], the
+    layout of mod) receive the sample's d gamma_pre / d beta sums (written, deterministic)"""
+    R, D = x.shape
+    call("pz_adaln_norm_bwd", _p(dh), dh.stride(0), _p(x), x.stride(0), _p(rstd), mod[:, gamma[0]:].data_ptr(),
+         _p(gamma[1]), _p(dres), _p(dx), dx.stride(0), None if dmod is None else dmod[:, gamma[0]:].data_ptr(),
+         None if dmod is None else dmod[:, beta:].data_ptr(), mod.stride(0), R, D, int(rows_per_sample), _st())
+    return dx
+
+
+def adaln_gate_bwd(dout, y, mod, gate, dy, dmod, rows_per_sample):
+    """backward of the gated branch: dy = dout * sigmoid(.), dmod[b, gate[0]:+D] = the sample's d gate_pre"""
+    R, D = y.shape
+    call("pz_adaln_gate_bwd", _p(dout), dout.stride(0), _p(y), y.stride(0), mod[:, gate[0]:].data_ptr(), _p(gate[1]),
+         _p(dy), dy.stride(0), dmod[:, gate[0]:].data_ptr(), mod.stride(0), R, D, int(rows_per_sample), _st())
+    return dy
+
+
 def act_bwd_colsum(dh, pre, dpre, act, ws, dbias, beta=False):
     """dpre = dh * act'(pre) (dpre may alias dh) and dbias (+)= colsum(dpre) in one pass; ws fp32 [rows >= 16, N]"""
     M, N = pre.shape

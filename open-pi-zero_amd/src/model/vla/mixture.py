@@ -7,7 +7,9 @@ The arena lays q|k|v and gate|up out adjacently; the native engine runs each
 layer as: RMSNorm -> fused QKV MFMA GEMM -> RoPE/split into the joint token
 buffers -> joint attention -> o_proj GEMM (+residual epilogue) -> RMSNorm ->
 fused gate|up GEMM with GeGLU epilogue -> down GEMM (+residual epilogue).
-adaLN(-Zero) modes are out of scope (adaptive_mode null).
+With ``adaptive_mode: adaLN | adaLN-Zero`` (the time-conditioned action expert, mixture.py:31-44,89-109) the
+three RMSNorms of the mixture are ``AdaptiveRMSNorm`` and, for adaLN-Zero, each layer carries the two
+``AdaptiveLayerscale`` gates; the engine then runs pz_adaln_fwd at those sites (csrc/pz_adaln.hip).
 """
 
 from __future__ import annotations
@@ -15,18 +17,31 @@ from __future__ import annotations
 from torch import nn
 
 from src.model.paligemma.modules import GemmaMLP, GemmaRMSNorm, GemmaRotaryEmbedding
+from src.model.vla.modules import AdaptiveLayerscale, AdaptiveRMSNorm
 from src.utils.config import cfg_get
+
+ADAPTIVE_MODES = ("adaLN", "adaLN-Zero")
+
+
+def _adaptive_mode(config):
+    mode = cfg_get(config, "adaptive_mode", None)
+    if mode and mode not in ADAPTIVE_MODES:
+        raise ValueError(f"adaptive_mode must be one of {ADAPTIVE_MODES} or null, got {mode!r}")
+    return mode or None
 
 
 class Mixture(nn.Module):
     def __init__(self, config):
         super().__init__()
-        if cfg_get(config, "adaptive_mode", None):
-            raise NotImplementedError("adaLN / adaLN-Zero action expert is out of scope (SURVEY 2.1)")
         self.layers = nn.ModuleList([MixtureDecoderLayer(config) for _ in range(cfg_get(config, "num_hidden_layers"))])
         self.adaptive_mode = None
         if cfg_get(config, "use_final_norm", False):
-            self.norm = GemmaRMSNorm(cfg_get(config, "hidden_size"), eps=float(cfg_get(config, "rms_norm_eps", 1e-6)))
+            self.adaptive_mode = _adaptive_mode(config)
+            hid, eps = cfg_get(config, "hidden_size"), float(cfg_get(config, "rms_norm_eps", 1e-6))
+            if self.adaptive_mode:
+                self.norm = AdaptiveRMSNorm(hid, cfg_get(config, "time_hidden_size"), eps=eps)
+            else:
+                self.norm = GemmaRMSNorm(hid, eps=eps)
 
     @property
     def head_dim(self) -> int:
@@ -39,10 +54,18 @@ class MixtureDecoderLayer(nn.Module):
         self.self_attn = MixtureAttention(config)
         self.mlp = GemmaMLP(config, use_quantize=cfg_get(config, "use_quantize", False),
                             use_lora=cfg_get(config, "use_lora", False))
-        self.adaptive_mode = None
-        eps = float(cfg_get(config, "rms_norm_eps", 1e-6))
-        self.input_layernorm = GemmaRMSNorm(cfg_get(config, "hidden_size"), eps=eps)
-        self.post_attention_layernorm = GemmaRMSNorm(cfg_get(config, "hidden_size"), eps=eps)
+        self.adaptive_mode = _adaptive_mode(config)
+        hid, eps = cfg_get(config, "hidden_size"), float(cfg_get(config, "rms_norm_eps", 1e-6))
+        if self.adaptive_mode:
+            tH = cfg_get(config, "time_hidden_size")
+            self.input_layernorm = AdaptiveRMSNorm(hid, tH, eps=eps)
+            self.post_attention_layernorm = AdaptiveRMSNorm(hid, tH, eps=eps)
+            if self.adaptive_mode == "adaLN-Zero":
+                self.post_adaptive_scale = AdaptiveLayerscale(hid, tH)
+                self.final_adaptive_scale = AdaptiveLayerscale(hid, tH)
+        else:
+            self.input_layernorm = GemmaRMSNorm(hid, eps=eps)
+            self.post_attention_layernorm = GemmaRMSNorm(hid, eps=eps)
 
 
 class MixtureAttention(nn.Module):

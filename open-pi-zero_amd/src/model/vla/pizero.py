@@ -44,6 +44,37 @@ def _resolve(root, dotted):
     return mod, parts[-1]
 
 
+def adaln_slots(prefix: str, n_layers: int, mode: str):
+    """Modulation layout of one adaLN mixture (``prefix`` = "joint_model.mixtures.<name>."): the names of its
+    time-conditioning Linears in arena order and the slot index of each site.  The biased Linears (every
+    to_gamma, and for adaLN-Zero the two layer-scale gates) come first, then the bias-free to_beta, so one
+    [B, time_hidden] x [time_hidden, nslots * hidden] GEMM gives every site's rows, one wgrad GEMM every weight
+    gradient and one column sum over the first ``len(b)`` slots every bias gradient.
+    Returns {"w": weight names, "b": bias names, "slot": {(layer | "norm", site): index}}."""
+    zero = mode == "adaLN-Zero"
+    w, b, beta, slot = [], [], [], {}
+
+    def biased(key, name):
+        slot[key] = len(w)
+        w.append(prefix + name + ".weight")
+        b.append(prefix + name + ".bias")
+
+    for l in range(n_layers):
+        p = f"layers.{l}."
+        biased((l, "in_g"), p + "input_layernorm.to_gamma.0")
+        biased((l, "post_g"), p + "post_attention_layernorm.to_gamma.0")
+        if zero:
+            biased((l, "post_z"), p + "post_adaptive_scale.to_adaln_zero_gamma")
+            biased((l, "final_z"), p + "final_adaptive_scale.to_adaln_zero_gamma")
+        beta += [((l, "in_b"), p + "input_layernorm.to_beta"), ((l, "post_b"), p + "post_attention_layernorm.to_beta")]
+    biased(("norm", "g"), "norm.to_gamma.0")
+    beta.append((("norm", "b"), "norm.to_beta"))
+    for key, name in beta:
+        slot[key] = len(w)
+        w.append(prefix + name + ".weight")
+    return {"w": w, "b": b, "slot": slot}
+
+
 class _PiZeroLoss(torch.autograd.Function):
     """Whole-model autograd node: native forward, native backward into the grad arena."""
 
@@ -89,15 +120,23 @@ class PiZero(nn.Module, NoSyncBase):
         self.final_action_clip_value = cfg_get(cfg, "final_action_clip_value", None)
         self.flow_sig_min = cfg_get(cfg, "flow_sig_min", 0.001)
         self.action_expert_adaptive_mode = cfg_get(cfg, "action_expert_adaptive_mode", None)
-        if self.action_expert_adaptive_mode:
-            raise NotImplementedError("adaLN action expert is out of scope (SURVEY 2.1)")
+        if self.action_expert_adaptive_mode not in (None, "adaLN", "adaLN-Zero"):
+            raise ValueError("action_expert_adaptive_mode must be adaLN, adaLN-Zero or null, got "
+                             f"{self.action_expert_adaptive_mode!r}")
+        for mix in ("proprio", "action"):  # pizero.py:76-84 conditions both expert mixtures or neither
+            if (cfg_get(cfg, f"mixture.{mix}.adaptive_mode", None) or None) != self.action_expert_adaptive_mode:
+                raise ValueError(f"mixture.{mix}.adaptive_mode must equal action_expert_adaptive_mode "
+                                 f"({self.action_expert_adaptive_mode!r})")
+        ada = bool(self.action_expert_adaptive_mode)
         with torch.device("meta"):
             self.embed_tokens = nn.Embedding(self.vocab_size, self.image_text_hidden_size, self.pad_token_id)
             self.vision_tower = instantiate(cfg_get(cfg, "vision"))
             self.multi_modal_projector = instantiate(cfg_get(cfg, "vision_projector"))
             self.joint_model = instantiate(cfg_get(cfg, "joint"))
-            self.action_encoder = ActionEncoder(self.action_dim, self.action_hidden_size, time_cond=True)
-            self.time_embedding = SinusoidalPosEmb(self.action_hidden_size, cfg_get(cfg, "time_max_period"))
+            # adaLN: the time embedding conditions the expert's norms instead of the action encoder (pizero.py:76-84)
+            self.action_encoder = ActionEncoder(self.action_dim, self.action_hidden_size, time_cond=not ada)
+            self.time_hidden_size = cfg_get(cfg, "time_hidden_size") if ada else self.action_hidden_size
+            self.time_embedding = SinusoidalPosEmb(self.time_hidden_size, cfg_get(cfg, "time_max_period"))
             self.proprio_encoder = nn.Linear(self.proprio_dim, self.proprio_hidden_size)
             self.action_decoder = nn.Linear(self.action_hidden_size, self.action_dim)
             if self.use_lm_head:  # optional text output (pizero.py:106-112), tied to embed_tokens
@@ -114,22 +153,32 @@ class PiZero(nn.Module, NoSyncBase):
         vL = len(self.vision_tower.vision_model.encoder.layers)
         mp = "joint_model.mixtures."
         out = []
+        ada = self.action_expert_adaptive_mode
 
         def gemma(mix, l, region):
             p = f"{mp}{mix}.layers.{l}."
             for n in ("mlp.down_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight",
                       "post_attention_layernorm.weight", "self_attn.o_proj.weight", "self_attn.q_proj.weight",
                       "self_attn.k_proj.weight", "self_attn.v_proj.weight", "input_layernorm.weight"):
+                if ada and mix != "vlm" and "layernorm" in n:
+                    continue  # AdaptiveRMSNorm has no weight vector: its Linears sit in the modulation block
                 out.append((p + n, region))
 
-        out += [("action_decoder.weight", "action"), ("action_decoder.bias", "action"),
-                (mp + "action.norm.weight", "action")]
-        if not self._tied:
-            out.append((mp + "proprio.norm.weight", "action"))
+        out += [("action_decoder.weight", "action"), ("action_decoder.bias", "action")]
+        if not ada:
+            out.append((mp + "action.norm.weight", "action"))
+            if not self._tied:
+                out.append((mp + "proprio.norm.weight", "action"))
         for l in reversed(range(nL)):
             gemma("action", l, "action")
             if not self._tied:
                 gemma("proprio", l, "action")
+        if ada:
+            # the time-conditioning Linears of a mixture, adjacent (adaln_slots): their gradients come from one wgrad
+            # GEMM and one column sum issued when the expert's layer-0 backward completes, hence this position
+            for mix in ("action",) if self._tied else ("action", "proprio"):
+                sl = adaln_slots(f"{mp}{mix}.", nL, ada)
+                out += [(n, "action") for n in sl["w"] + sl["b"]]
         for n in ("action_encoder.linear_3", "action_encoder.linear_2", "action_encoder.linear_1", "proprio_encoder"):
             out += [(n + ".weight", "action"), (n + ".bias", "action")]
         if hasattr(self.joint_model.mixtures["vlm"], "norm"):  # use_final_norm (text generation config)
@@ -178,10 +227,13 @@ class PiZero(nn.Module, NoSyncBase):
         g = torch.Generator(device="cpu").manual_seed(0)
         for name in self._arena.order:
             v = self._arena.view(name)
+            if "to_adaln_zero_gamma" in name:  # AdaptiveLayerscale: weight 0, bias -2 (vla/modules.py:107-109)
+                v.fill_(0.0 if name.endswith("weight") else -2.0)
+                continue
             if "layer_norm" in name or "post_layernorm" in name:
                 v.fill_(1.0 if name.endswith("weight") else 0.0)
                 continue
-            if name.endswith("norm.weight") or "layernorm" in name:
+            if (name.endswith("norm.weight") or "layernorm" in name) and "to_gamma" not in name and "to_beta" not in name:
                 v.zero_()
                 continue
             if name in ("embed_tokens.weight", "vision_tower.vision_model.embeddings.position_embedding.weight"):
@@ -261,6 +313,10 @@ class PiZero(nn.Module, NoSyncBase):
         mixture and the action expert: prefill MLP GEMMs W8A8 on the fp8 MFMA (per-row activation scales),
         prefill q|k|v / o projections and denoise rows W8A16.  Training never uses them.  The codes are a snapshot of the current weights:
         call again after the weights change.  An extension: the reference has no fp8 path."""
+        if enabled and self.action_expert_adaptive_mode:
+            from pizero_native.engine import FP8_ADAPTIVE_MSG
+
+            raise NotImplementedError(FP8_ADAPTIVE_MSG)
         self._fp8_infer = bool(enabled)
         eng = self._engine()
         if enabled:
@@ -520,7 +576,11 @@ class PiZero(nn.Module, NoSyncBase):
     def infer_action(self, input_ids, pixel_values, image_text_proprio_mask, action_mask, vlm_position_ids,
                      proprio_position_ids, action_position_ids, proprios, noise: Optional[torch.Tensor] = None,
                      clip: bool = True):
-        """pizero.py:416-490: prefill caches vlm+proprio K/V once, 10 Euler steps on the action expert."""
+        """pizero.py:416-490: prefill caches vlm+proprio K/V once, 10 Euler steps on the action expert.
+        With an adaLN expert (action_expert_adaptive_mode) the reference's cached path raises AttributeError
+        ('NoneType' object has no attribute 'ndim': its prefill runs the proprio mixture without the time condition)
+        and cannot work, since the proprio K/V depend on t: here it computes infer_action_naive's result -- the vlm
+        K/V cached once, the proprio + action rows re-run with cond(t) every Euler step."""
         dev = self._dev()
         B = input_ids.shape[0]
         dtype = pixel_values.dtype
@@ -544,7 +604,8 @@ class PiZero(nn.Module, NoSyncBase):
                            action_position_ids, proprios, noise: Optional[torch.Tensor] = None, clip: bool = True):
         """pizero.py:492-557.  Re-running the prefix every step gives identical math (the vlm/proprio rows
         never attend to actions), so the native path reuses the cached prefix (fp32-exact equivalence:
-        SURVEY 8(c) measured |naive - cached| = 1.8e-7)."""
+        SURVEY 8(c) measured |naive - cached| = 1.8e-7).  With an adaLN expert only the vlm rows are cached: the
+        proprio rows depend on t and are re-run with the action rows in every Euler step (see infer_action)."""
         itp, amask = self.split_full_mask_into_submasks(causal_mask)
         return self.infer_action(input_ids, pixel_values, itp, amask, vlm_position_ids, proprio_position_ids,
                                  action_position_ids, proprios, noise=noise, clip=clip)
