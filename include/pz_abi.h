@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PZ_ABI_VERSION 21
+#define PZ_ABI_VERSION 22
 
 enum {
   PZ_OK = 0,
@@ -86,6 +86,16 @@ typedef struct pz_gemm_args {
    *   2 = W8A16: bf16 A rows (M <= 64, optional fused RMSNorm), fp8 B [N][K] expanded to bf16 in
    *       registers, product * alpha (= the weight scale); K % 64 == 0, ldb % 16 == 0. */
   int32_t fp8_mode; const float* a_row_scale;
+  /* (ABI 22) rank extension (LoRA adapters, lora.py:141-211): a second operand pair summed into the accumulators
+   * after the main K-tiles and BEFORE alpha / bias / resid / aux / the epilogue,
+   *   acc(m,n) = sum_{k<K} A(m,k) B(k,n) + sum_{j<K2} A2(m,j) B2(j,n),
+   * A2 / B2 addressed like A / B (a_kcontig / b_kcontig) with lda2 / ldb2 (% 8 == 0, 16-byte aligned).
+   * K2 % 8 == 0, 8 <= K2 <= 384, batch 1, bf16 operands (fp8_mode != 0: PZ_ERR_UNSUPPORTED), no fused norm.
+   * Runs the 8-phase 256-tile kernel (A k-contiguous, K % 8 == 0, enough tiles) or the 128-tile kernel, never the
+   * row-slab / tall / skinny / GEMV / split-K paths.  All zero: off, and pz_gemm is exactly the ABI 21 one. */
+  const void* A2; int64_t lda2;
+  const void* B2; int64_t ldb2;
+  int64_t K2;
 } pz_gemm_args;
 int pz_gemm(const pz_gemm_args* args, void* stream);
 /* fp8 (OCP e4m3fn) quantisation for fp8_mode 1 / 2 (C5, BASELINE.json configs[4]):
@@ -195,6 +205,11 @@ typedef struct pz_qkv_rope_args {
   /* (ABI 15) w_fp8 = 1: W holds OCP e4m3 codes [N][K] (ldw in codes) with the per-tensor scale w_scale (the fp8
    * inference weights of C5); pz_gemm_qkv_rope's few-row path only (W8A16), 0 everywhere else */
   int32_t w_fp8; float w_scale;
+  /* (ABI 22) rank extension as in pz_gemm_args: x2 [M][K2] (ldx2), W2 [N][K2] (ldw2), summed before the rounding
+   * and RoPE; 8-phase path only (PZ_ERR_UNSUPPORTED for the few-row shapes and with fp8 weights) */
+  const void* x2; int64_t ldx2;
+  const void* W2; int64_t ldw2;
+  int64_t K2;
 } pz_qkv_rope_args;
 int pz_gemv_qkv_rope(const pz_qkv_rope_args* a, void* stream);
 /* The same fused projection + RoPE + scatter for MANY rows (training / prefill, mixture.py:162-215,
@@ -439,6 +454,18 @@ int pz_adaln_norm_bwd(const void* dh, int64_t lddh, const void* x, int64_t ldx, 
 int pz_adaln_gate_bwd(const void* dout, int64_t lddo, const void* y, int64_t ldy, const float* gate_pre,
                       const void* gate_bias, void* dy, int64_t lddy, float* dgate_pre, int64_t ldmod, int64_t R,
                       int64_t D, int64_t rows_per_sample, void* stream);
+
+/* (ABI 22) rank-r weight gradient of a LoRA adapter (lora.py:141-211 autograd; csrc/pz_lora.hip):
+ *   out[j*ld_out + d] (+)= alpha * sum_m P[m*ldp + j] * Q[m*ldq + d]      (transposed: out[d*ld_out + j])
+ * Q bf16 [M, D] (the big operand: x for dA = v^T x, dy for dB = dy^T u with transposed = 1), P bf16 [M, R]
+ * (v = dy B or u = x A^T), out bf16, fp32 accumulation.  R % 8 == 0, R <= 128, D % 8 == 0, ldq / ldp % 8 == 0,
+ * Q / P 16-byte aligned; beta = 1 accumulates into out.  Q is read once: the M rows are dealt to workgroups in a
+ * fixed partition whose fp32 partials go to ws (pz_lora_wgrad_ws_bytes(M, D, R) bytes, 16-byte aligned) and are
+ * summed in a fixed order by a second kernel.  No atomics: bitwise repeatable. */
+int64_t pz_lora_wgrad_ws_bytes(int64_t M, int64_t D, int64_t R);
+int pz_lora_wgrad(const void* Q, int64_t ldq, const void* P, int64_t ldp, void* out, int64_t ld_out, int64_t M,
+                  int64_t D, int64_t R, int32_t transposed, float alpha, int32_t beta, void* ws, int64_t ws_bytes,
+                  void* stream);
 
 /* test instrument: fill every CU's LDS with `word` (0xffffffff = NaN) on `stream`, so the next kernel's reads of
  * LDS it did not write return NaN (tests/test_train_loop_gpu.py; _lib.call runs it before every launch under

@@ -115,9 +115,9 @@ __device__ __forceinline__ bf16x8 frag(const char* lds, int rb, int kk, int lane
 }
 
 
-// TAG only separates kernel symbols (profiling): 1 = the Gemma-2B MLP gate|up GeGLU GEMM (M >= 2048 rows)
-template <bool AKC, bool BKC, int WM, int TAG>
-__global__ void __launch_bounds__(NT, 2) gemm_kernel(GemmP p) {
+// EXT: the rank extension's K-tiles (A2 / B2 / K2) follow the main ones; no split-K, no batch
+template <bool AKC, bool BKC, int WM, bool EXT>
+__device__ __forceinline__ void gemm_body(const GemmP& p) {
   constexpr int WN = 4 / WM;
   constexpr int MI = (BM / WM) / 16;  // m blocks per wave
   constexpr int NI = (BN / WN) / 16;  // n blocks per wave
@@ -157,10 +157,19 @@ __global__ void __launch_bounds__(NT, 2) gemm_kernel(GemmP p) {
 #pragma unroll
     for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nk = (int)((kend - kbeg + BK - 1) / BK);
+  const int nk1 = (int)((kend - kbeg + BK - 1) / BK);
+  const int nk = EXT ? nk1 + (int)((p.K2 + BK - 1) / BK) : nk1;
   u32x4 ra[4], rb[4];
-  g2r<AKC>(ra, A, p.lda, m0, p.M, kbeg, kend, false, 0);
-  g2r<BKC>(rb, B, p.ldb, n0, p.N, kbeg, kend, geglu, p.geglu_I);
+  auto load = [&](int kt) {
+    if (EXT && kt >= nk1) {
+      g2r<AKC>(ra, p.A2, p.lda2, m0, p.M, (int64_t)(kt - nk1) * BK, p.K2, false, 0);
+      g2r<BKC>(rb, p.B2, p.ldb2, n0, p.N, (int64_t)(kt - nk1) * BK, p.K2, geglu, p.geglu_I);
+    } else {
+      g2r<AKC>(ra, A, p.lda, m0, p.M, kbeg + (int64_t)kt * BK, kend, false, 0);
+      g2r<BKC>(rb, B, p.ldb, n0, p.N, kbeg + (int64_t)kt * BK, kend, geglu, p.geglu_I);
+    }
+  };
+  load(0);
   r2s<AKC>(ra, sA);
   r2s<BKC>(rb, sB);
   __syncthreads();
@@ -168,10 +177,7 @@ __global__ void __launch_bounds__(NT, 2) gemm_kernel(GemmP p) {
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     const bool more = kt + 1 < nk;
-    if (more) {
-      g2r<AKC>(ra, A, p.lda, m0, p.M, kbeg + (int64_t)(kt + 1) * BK, kend, false, 0);
-      g2r<BKC>(rb, B, p.ldb, n0, p.N, kbeg + (int64_t)(kt + 1) * BK, kend, geglu, p.geglu_I);
-    }
+    if (more) load(kt + 1);
     const char* a_img = sA + cur * TILE_BYTES;
     const char* b_img = sB + cur * TILE_BYTES;
 #pragma unroll
@@ -241,6 +247,18 @@ __global__ void __launch_bounds__(NT, 2) gemm_kernel(GemmP p) {
         store_out4_m<EM>(p, cofs, rofs, m, n0 + wn * (BN / WN) + j * 16 + 4 * (lane >> 4), acc[i][j]);
     }
   });
+}
+
+// TAG only separates kernel symbols (profiling): 1 = the Gemma-2B MLP gate|up GeGLU GEMM (M >= 2048 rows)
+template <bool AKC, bool BKC, int WM, int TAG>
+__global__ void __launch_bounds__(NT, 2) gemm_kernel(GemmP p) {
+  gemm_body<AKC, BKC, WM, false>(p);
+}
+
+// ... with the rank extension (pz_gemm_args.K2 > 0)
+template <bool AKC, bool BKC, int WM>
+__global__ void __launch_bounds__(NT, 2) gemm_x_kernel(GemmP p) {
+  gemm_body<AKC, BKC, WM, true>(p);
 }
 
 // split-K second pass: C = epilogue(sum_z ws[z]) -- one thread per (row, 4 columns)
@@ -1026,10 +1044,15 @@ __device__ __forceinline__ void epilogue8p(const GemmP& p, int64_t cofs, int64_t
 // twice the bf16 MFMA rate.  The per-row activation scale (p.rs) multiplies the accumulators after
 // the main loop (before the split-tail partials are written, so the tail sum stays linear); the
 // weight scale is alpha.
-template <bool AKC, bool BKC, bool GEGLU, bool KTAIL, bool F8>
+// EXT (rank extension, KTAIL instantiation, whole tiles only): the ceil(K2 / 64) K-tiles of A2 / B2 follow the
+// ceil(K / 64) main ones through the same pipeline -- only the DMA source of a tile changes -- and the K-tail
+// clamping / masking applies to the last tile of EACH range (K % 8 == 0; K2 % 8 == 0, K2 >= 8).
+template <bool AKC, bool BKC, bool GEGLU, bool KTAIL, bool F8, bool EXT = false>
 __device__ __forceinline__ void gemm8p_body(const GemmP& p) {
+  static_assert(!EXT || (KTAIL && !F8), "rank extension: bf16, tail-capable instantiation");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nk_all = (int)((p.K + 63) / 64);
+  const int nk1 = (int)((p.K + 63) / 64);  // main K-tiles
+  const int nk_all = EXT ? nk1 + (int)((p.K2 + 63) / 64) : nk1;
   int lid = blockIdx.x, piece = -1, kt0 = 0, nk = nk_all;
   if (p.tail_s && lid >= p.dp_tiles) {  // split tail: one K-piece of a leftover tile
     const int u = lid - p.dp_tiles;
@@ -1061,6 +1084,20 @@ __device__ __forceinline__ void gemm8p_body(const GemmP& p) {
   }
   const int64_t stepA = AKC ? 64 : 64 * p.lda;
   const int64_t stepB = BKC ? 64 : 64 * p.ldb;
+  // extension sources of the same lanes (K-tile kt >= nk1 reads tile kt - nk1 of A2 / B2)
+  // (these 16 VGPRs push the EXT instantiations from 236 to 256 VGPRs with 11-25 spilled: profiles/lora/README.txt)
+  const bf16_t* src2[4][2];
+  const int64_t stepA2 = AKC ? 64 : 64 * p.lda2;
+  const int64_t stepB2 = BKC ? 64 : 64 * p.ldb2;
+  if (EXT) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      src2[0][i] = p8_src<AKC, true, false>(p.A2, p.lda2, 0, i, t, m0, p.M, 0);
+      src2[3][i] = p8_src<AKC, true, false>(p.A2, p.lda2, 1, i, t, m0, p.M, 0);
+      src2[1][i] = p8_src<BKC, false, GEGLU>(p.B2, p.ldb2, 0, i, t, n0, p.N, p.geglu_I);
+      src2[2][i] = p8_src<BKC, false, GEGLU>(p.B2, p.ldb2, 1, i, t, n0, p.N, p.geglu_I);
+    }
+  }
   if (kt0) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -1075,17 +1112,32 @@ __device__ __forceinline__ void gemm8p_body(const GemmP& p) {
   // tensor (finite data) and the A fragments of k >= krem are zeroed before the MFMAs.
   // (KTAIL = false instantiations assume K % 64 == 0 and carry none of this code; a K-piece
   // that does not end the reduction has no tail)
-  const int krem = (KTAIL && kt0 + nk == nk_all) ? (int)(p.K - (int64_t)(nk_all - 1) * 64) : 64;  // 1..64
+  const int krem = EXT ? (int)(p.K2 - (int64_t)(nk_all - nk1 - 1) * 64)
+                       : (KTAIL && kt0 + nk == nk_all) ? (int)(p.K - (int64_t)(nk_all - 1) * 64) : 64;  // 1..64
+  const int krem1 = EXT ? (int)(p.K - (int64_t)(nk1 - 1) * 64) : 64;  // EXT: valid k of the last MAIN tile
   auto issue = [&](int piece, int kt) {
     char* dst = smem + (kt & 1) * P8_BUF + lds_off[piece] + wave * 1024;
     const bool isA = piece == 0 || piece == 3;
     const int64_t step = isA ? stepA : stepB;
     const bool kc = isA ? AKC : BKC;
     const int region = (piece == 3 || piece == 2) ? 1 : 0;
+    const bool ext = EXT && kt >= nk1;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const bf16_t* g = src[piece][i] + kt * step;
-      if (KTAIL && krem < 64 && kt == nk - 1) {
+      const bf16_t* g = ext ? src2[piece][i] + (kt - nk1) * (isA ? stepA2 : stepB2) : src[piece][i] + kt * step;
+      if constexpr (EXT) {  // the last tile of the main range and of the extension range may both be partial
+        const int kr = kt == nk1 - 1 ? krem1 : (kt == nk - 1 ? krem : 64);
+        if (kr < 64) {
+          if (kc) {
+            const int r = i * 64 + (t >> 3);
+            const int kl = 8 * ((t & 7) ^ ((r >> 1) & 7));
+            if (kl >= kr) g -= kl - (kr - 8);
+          } else {
+            const int kl = region * 32 + i * 16 + (t >> 5);
+            if (kl >= kr) g -= (int64_t)(kl - (kr - 1)) * (ext ? (isA ? p.lda2 : p.ldb2) : (isA ? p.lda : p.ldb));
+          }
+        }
+      } else if (KTAIL && krem < 64 && kt == nk - 1) {
         if (kc) {  // this lane's 8 k: 8 * chunk within the tile
           const int r = i * 64 + (t >> 3);
           const int kl = 8 * ((t & 7) ^ ((r >> 1) & 7));
@@ -1106,7 +1158,16 @@ __device__ __forceinline__ void gemm8p_body(const GemmP& p) {
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   bf16x8 af[4][2], bf[2][2][2];  // A quadrant rows (4 x 16) x kk;  B [bh][2 x 16 cols][kk]
   auto mask_tail_a = [&](int kt) {
-    if (KTAIL && krem < 64 && kt == nk - 1) {
+    if constexpr (EXT) {
+      const int kr = kt == nk1 - 1 ? krem1 : (kt == nk - 1 ? krem : 64);
+      if (kr < 64) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk)
+            if (kk * 32 + 8 * (lane >> 4) >= kr) af[i][kk] = bf16x8{};
+      }
+    } else if (KTAIL && krem < 64 && kt == nk - 1) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1332,6 +1393,12 @@ __device__ __forceinline__ void gemm8p_body(const GemmP& p) {
 template <bool AKC, bool BKC, bool GEGLU, bool KTAIL>
 __global__ void __launch_bounds__(NT2, 1) gemm8p_kernel(GemmP p) {
   gemm8p_body<AKC, BKC, GEGLU, KTAIL, false>(p);
+}
+
+// ... with the rank extension (pz_gemm_args.K2 > 0, pz_qkv_rope_args.K2 > 0)
+template <bool AKC, bool BKC, bool GEGLU>
+__global__ void __launch_bounds__(NT2, 1) gemm8p_x_kernel(GemmP p) {
+  gemm8p_body<AKC, BKC, GEGLU, true, false, true>(p);
 }
 
 // fp8 e4m3 x e4m3 (W8A8) instantiation of the 8-phase kernel (C5 prefill MLP GEMMs)
@@ -1827,6 +1894,21 @@ static int launch_tile(const GemmP& p, int64_t batch, hipStream_t st) {
   return PZ_OK;
 }
 
+// rank-extended 128-tile kernel: whole K, batch 1
+template <bool AKC, bool BKC, int WM>
+static int launch_tile_x(const GemmP& p, hipStream_t st) {
+  const int smem = 4 * TILE_BYTES;
+  auto kern = gemm_x_kernel<AKC, BKC, WM>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n, 1), dim3(NT), smem, st, p);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
 template <bool AKC, bool BKC, bool GEGLU>
 static int launch256(const GemmP& p, int64_t batch, hipStream_t st) {
   const int smem = 2 * 2 * 256 * 64 * 2;  // 128 KiB for either pipeline
@@ -2024,6 +2106,23 @@ Plan make_plan(const pz_gemm_args* a) {
   pl.bkc = a->b_kcontig != 0;
   pl.geglu = a->epilogue == PZ_EPI_GEGLU;
   const int64_t ncols = pl.geglu ? a->geglu_inter : a->N;
+  // rank extension (K2 > 0): only the 8-phase kernel (whole tiles, A k-contiguous, K % 8 == 0, the usual row /
+  // column / workgroup thresholds) and the 128-tile kernel (whole K) carry it; every other path is skipped
+  if (a->K2 > 0) {
+    const int64_t cwx = pl.geglu ? BT / 2 : BT;
+    const int64_t tm = (a->M + BT - 1) / BT, tn = (ncols + cwx - 1) / cwx;
+    if (use_8phase() && pl.akc && a->K % 8 == 0 && a->M >= 512 && ncols >= (pl.geglu ? 256 : 512) && tm * tn >= 160) {
+      pl.kind = PATH_256;
+      pl.tiles_m = tm;
+      pl.tiles_n = tn;
+      return pl;
+    }
+    pl.kind = PATH_TILE;
+    pl.tiles_m = (a->M + BM - 1) / BM;
+    pl.tiles_n = (ncols + (pl.geglu ? BN / 2 : BN) - 1) / (pl.geglu ? BN / 2 : BN);
+    pl.wm = pl.geglu ? 4 : 2;
+    return pl;
+  }
   // fp8 W8A8: the 8-phase 256-tile kernel on code pairs (K, lda, ldb halved by the caller of make_plan); the row-slab
   // shapes (64 < M <= 1024, <= 2048 codes of K in 128-code chunks, <= 4096 columns, no GeGLU: C5's prefill q|k|v / o)
   // take the W8A8 row-slab kernel (PZ_ROWS_W8A8=0: the 8-phase kernel, A/B; read per call)
@@ -2219,7 +2318,9 @@ extern "C" const char* pz_gemm_kernel_name(const pz_gemm_args* a) {
       snprintf(buf, sizeof(buf), "gemv_kernel<M<=%d>", a->M <= 4 ? 4 : 8);
       break;
     case PATH_256:
-      if (use_8phase() && pl.tail_s)
+      if (a->K2 > 0)
+        snprintf(buf, sizeof(buf), "gemm8p_x_kernel<%s, %s, %s>", bstr(pl.akc), bstr(pl.bkc), bstr(pl.geglu));
+      else if (use_8phase() && pl.tail_s)
         snprintf(buf, sizeof(buf), "%s<%s, %s, %s, %s>+gemm8p_tail_epilogue(tail %lld x %d)",
                  use_khalf(pl.akc, pl.bkc, a->M, a->N, a->K) ? "gemm8k_kernel" : "gemm8p_kernel", bstr(pl.akc), bstr(pl.bkc), bstr(pl.geglu), bstr(a->K % 64 != 0),
                  (long long)(pl.tiles_m * pl.tiles_n - pl.dp_tiles), pl.tail_s);
@@ -2231,7 +2332,8 @@ extern "C" const char* pz_gemm_kernel_name(const pz_gemm_args* a) {
                  BK256);
       break;
     case PATH_TILE:
-      snprintf(buf, sizeof(buf), "gemm_kernel<%s, %s, %d, %d>", bstr(pl.akc), bstr(pl.bkc), pl.wm, pl.tag);
+      if (a->K2 > 0) snprintf(buf, sizeof(buf), "gemm_x_kernel<%s, %s, %d>", bstr(pl.akc), bstr(pl.bkc), pl.wm);
+      else snprintf(buf, sizeof(buf), "gemm_kernel<%s, %s, %d, %d>", bstr(pl.akc), bstr(pl.bkc), pl.wm, pl.tag);
       break;
     case PATH_ROWS:
       if (pl.rows_f8 == 2)
@@ -2364,6 +2466,21 @@ static int launch8p(const GemmP& p, int64_t batch, hipStream_t st) {
   return launch8p_k<AKC, BKC, GEGLU, false>(p, batch, st);
 }
 
+// rank-extended 8-phase kernel: whole tiles, batch 1
+template <bool BKC, bool GEGLU>
+static int launch8p_x(const GemmP& p, hipStream_t st) {
+  const int smem = 2 * P8_BUF;
+  auto kern = gemm8p_x_kernel<true, BKC, GEGLU>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n, 1), dim3(NT2), smem, st, p);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
 // large-GEMM kernel: the 8-phase ping-pong (default) or the 2-stage 256 kernel (PZ_GEMM_BIG=2stage, A/B runs)
 static bool use_8phase() {
   const char* e = getenv("PZ_GEMM_BIG");  // read per call: A/B runs flip it in-process
@@ -2408,6 +2525,19 @@ extern "C" int pz_gemm(const pz_gemm_args* a, void* stream) {
   if (a->aux) PZ_CHECK_ARG(a->ld_aux % 4 == 0 && PZ_ALIGNED(a->aux, 8), "pz_gemm: aux alignment");
   PZ_CHECK_ARG(a->ws_bytes >= 0, "pz_gemm: negative ws_bytes");
   PZ_CHECK_ARG(a->fp8_mode >= 0 && a->fp8_mode <= 2, "pz_gemm: fp8_mode %d", (int)a->fp8_mode);
+  PZ_CHECK_ARG(a->K2 >= 0, "pz_gemm: negative K2");
+  if (a->K2 > 0) {
+    if (a->fp8_mode != 0) {
+      pz_set_error("pz_gemm: the rank extension (K2 > 0) takes bf16 operands only");
+      return PZ_ERR_UNSUPPORTED;
+    }
+    PZ_CHECK_ARG(a->K2 % 8 == 0 && a->K2 >= 8 && a->K2 <= 384, "pz_gemm: K2 = %lld must be a multiple of 8 in [8, 384]",
+                 (long long)a->K2);
+    PZ_CHECK_ARG(a->A2 && a->B2 && PZ_ALIGNED(a->A2, 16) && PZ_ALIGNED(a->B2, 16) && a->lda2 % 8 == 0 &&
+                     a->ldb2 % 8 == 0,
+                 "pz_gemm: A2 / B2 must be 16-byte aligned with lda2 / ldb2 %% 8 == 0");
+    PZ_CHECK_ARG(a->batch == 1 && !a->norm_w, "pz_gemm: the rank extension is unbatched and takes no fused norm");
+  }
   pz_gemm_args a8;  // fp8 W8A8: K / lda / ldb in code pairs for the planner and the kernel
   if (a->fp8_mode == 1) {
     PZ_CHECK_ARG(a->a_kcontig && a->b_kcontig && a->batch == 1 && !a->norm_w && a->epilogue <= PZ_EPI_SILU &&
@@ -2452,6 +2582,11 @@ extern "C" int pz_gemm(const pz_gemm_args* a, void* stream) {
   p.nw = (const bf16_t*)a->norm_w;
   p.neps = a->norm_eps;
   p.rs = a->fp8_mode == 1 ? a->a_row_scale : nullptr;
+  if (a->K2 > 0) {
+    p.A2 = (const bf16_t*)a->A2;
+    p.B2 = (const bf16_t*)a->B2;
+    p.lda2 = a->lda2; p.ldb2 = a->ldb2; p.K2 = a->K2;
+  }
   {
     const char* e = getenv("PZ_GEMM_DBG");
     p.dbg = e ? atoi(e) : 0;
@@ -2526,6 +2661,17 @@ extern "C" int pz_gemm(const pz_gemm_args* a, void* stream) {
     }
     return pz_tall_launch(p, pl.tall_mi, geglu, pl.bkc, pl.splits > 1 ? pl.splits : 1, st);
   }
+  if (a->K2 > 0) {
+    if (pl.kind == PATH_256) {
+      if (geglu) return launch8p_x<true, true>(p, st);
+      return a->b_kcontig ? launch8p_x<true, false>(p, st) : launch8p_x<false, false>(p, st);
+    }
+    if (geglu) return a->a_kcontig ? launch_tile_x<true, true, 4>(p, st) : launch_tile_x<false, true, 4>(p, st);
+    if (a->a_kcontig && a->b_kcontig) return launch_tile_x<true, true, 2>(p, st);
+    if (a->a_kcontig && !a->b_kcontig) return launch_tile_x<true, false, 2>(p, st);
+    if (!a->a_kcontig && a->b_kcontig) return launch_tile_x<false, true, 2>(p, st);
+    return launch_tile_x<false, false, 2>(p, st);
+  }
   if (pl.kind == PATH_256 && use_8phase()) {
     if (pl.tail_s) {
       p.ws = (float*)a->workspace;
@@ -2592,6 +2738,15 @@ extern "C" int pz_gemm_qkv_rope(const pz_qkv_rope_args* a, void* stream) {
   g.alpha = 1.f;
   g.norm_w = a->norm_w;
   g.norm_eps = a->norm_eps;
+  if (a->K2 > 0) {
+    if (a->w_fp8 || a->norm_w) return PZ_ERR_UNSUPPORTED;
+    PZ_CHECK_ARG(a->K2 % 8 == 0 && a->K2 >= 8 && a->K2 <= 384 && a->x2 && a->W2 && PZ_ALIGNED(a->x2, 16) &&
+                     PZ_ALIGNED(a->W2, 16) && a->ldx2 % 8 == 0 && a->ldw2 % 8 == 0,
+                 "gemm_qkv_rope: rank extension needs K2 %% 8 == 0 in [8, 384], 16-byte aligned x2 / W2");
+    g.A2 = a->x2; g.lda2 = a->ldx2;
+    g.B2 = a->W2; g.ldb2 = a->ldw2;
+    g.K2 = a->K2;
+  }
   if (a->w_fp8) {
     PZ_CHECK_ARG(a->ldw % 16 == 0, "gemm_qkv_rope: fp8 weights need ldw %% 16 == 0");
     g.fp8_mode = 2;
@@ -2641,6 +2796,12 @@ extern "C" int pz_gemm_qkv_rope(const pz_qkv_rope_args* a, void* stream) {
   p.rk = (bf16_t*)a->k_out;
   p.rv = (bf16_t*)a->v_out;
   p.rT = a->T; p.rnh = a->nh; p.rLq = a->Lq; p.rqoff = a->qoff; p.rLk = a->Lk; p.rkoff = a->koff;
+  if (a->K2 > 0) {
+    p.A2 = (const bf16_t*)a->x2;
+    p.B2 = (const bf16_t*)a->W2;
+    p.lda2 = a->ldx2; p.ldb2 = a->ldw2; p.K2 = a->K2;
+    return launch8p_x<true, false>(p, (hipStream_t)stream);
+  }
   return launch8p<true, true, false>(p, 1, (hipStream_t)stream);
 }
 

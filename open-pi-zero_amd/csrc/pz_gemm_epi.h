@@ -53,6 +53,11 @@ struct GemmP {
   int nt_aux;
   // super-row height of the 8-phase kernels' tile order (tile_coords; PZ_GEMM_GROUP, read per call; default 8)
   int group;
+  // rank extension (ABI 22; LoRA adapters): acc += sum_{j < K2} A2(m, j) B2(j, n) with the k-contiguity of A / B,
+  // accumulated after the main K-tiles by the *_x kernels (gemm_x_kernel, gemm8p_x_kernel).  K2 == 0: off.
+  const bf16_t* A2;
+  const bf16_t* B2;
+  int64_t lda2, ldb2, K2;
 };
 
 namespace {

@@ -19,7 +19,7 @@ if os.environ.get("PZ_LIB_PATH"):
     print(f"[pizero_native] PZ_LIB_PATH override: loading {LIB_PATH} instead of the default libpizero_hip.so",
           file=_sys.stderr, flush=True)
 
-ABI_VERSION = 21  # include/pz_abi.h PZ_ABI_VERSION
+ABI_VERSION = 22  # include/pz_abi.h PZ_ABI_VERSION
 PZ_EPI_NONE, PZ_EPI_GELU, PZ_EPI_GEGLU, PZ_EPI_SILU = 0, 1, 2, 3
 PZ_EPI_DGELU, PZ_EPI_DSILU, PZ_EPI_DGEGLU = 4, 5, 6
 PZ_SUMSQ_PARTS = 2048  # include/pz_abi.h
@@ -43,6 +43,7 @@ class GemmArgs(C.Structure):
         ("workspace", vp), ("ws_bytes", i64),
         ("norm_w", vp), ("norm_eps", f32),
         ("fp8_mode", i32), ("a_row_scale", vp),
+        ("A2", vp), ("lda2", i64), ("B2", vp), ("ldb2", i64), ("K2", i64),
     ]
 
 
@@ -102,6 +103,7 @@ class QkvRopeArgs(C.Structure):
         ("norm_w", vp), ("norm_eps", f32), ("pos", vp), ("cs", vp), ("q_out", vp), ("k_out", vp), ("v_out", vp),
         ("T", i64), ("nh", i64), ("hd", i64), ("Lq", i64), ("qoff", i64), ("Lk", i64), ("koff", i64),
         ("w_fp8", i32), ("w_scale", f32),
+        ("x2", vp), ("ldx2", i64), ("W2", vp), ("ldw2", i64), ("K2", i64),
     ]
 
 
@@ -181,13 +183,15 @@ SIGNATURES = {
     "pz_adaln_fwd": [vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, f32, vp],
     "pz_adaln_norm_bwd": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, i64, i64, vp],
     "pz_adaln_gate_bwd": [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, vp],
+    "pz_lora_wgrad_ws_bytes": [i64, i64, i64],
+    "pz_lora_wgrad": [vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, f32, i32, vp, i64, vp],
     "pz_debug_poison_lds": [C.c_uint32, vp],
     "pz_debug_spin": [i64, i64, vp],
     "pz_last_error": [],
     "pz_abi_version": [],
 }
 _RESTYPE = {"pz_last_error": C.c_char_p, "pz_gemm_kernel_name": C.c_char_p, "pz_norm_rows_per_part": i64,
-            "pz_decode_attn_ws_bytes": i64}
+            "pz_decode_attn_ws_bytes": i64, "pz_lora_wgrad_ws_bytes": i64}
 
 _lib = None
 
@@ -217,7 +221,7 @@ def lib():
 
 # entry points that enqueue no kernel (everything else takes the stream as its last argument)
 _NO_LAUNCH = {"pz_last_error", "pz_abi_version", "pz_gemm_kernel_name", "pz_norm_rows_per_part",
-              "pz_decode_attn_ws_bytes", "pz_debug_poison_lds"}
+              "pz_decode_attn_ws_bytes", "pz_lora_wgrad_ws_bytes", "pz_debug_poison_lds"}
 # test instrument (tests/test_train_loop_gpu.py): with a word set, every launch is preceded on its stream by
 # pz_debug_poison_lds(word), so a kernel reading LDS it did not write sees NaN.  PZ_POISON_LDS=1 turns it on
 # for a whole process (0xffffffff).

@@ -21,9 +21,11 @@ import torch.distributed as dist
 
 
 class GradReducer:
-    def __init__(self, arena, region_marks, bucket_bytes=256 << 20, group=None):
-        """region_marks: {(stage, layer): {region: end_offset}} -> prefix ends that are final."""
+    def __init__(self, arena, region_marks, bucket_bytes=256 << 20, group=None, skip_regions=()):
+        """region_marks: {(stage, layer): {region: end_offset}} -> prefix ends that are final.
+        skip_regions: regions without a trainable parameter, never reduced (LoRA: the frozen base VLM weights)."""
         self.arena = arena
+        self.skip = frozenset(skip_regions)
         self.marks = region_marks
         self.bucket = bucket_bytes
         self.group = group
@@ -40,7 +42,9 @@ class GradReducer:
         self._reset()
 
     def _reset(self):
-        self.done = {r: self.arena.region_range[r][0] for r in ("action", "vlm") if r in self.arena.region_range}
+        # "lora": the adapters of a LoRA model (one region behind the VLM weights, final when the backward ends)
+        self.done = {r: self.arena.region_range[r][0] for r in ("action", "vlm", "lora")
+                     if r in self.arena.region_range and r not in self.skip}
         self.final = dict(self.done)
         self.handles = []
 
@@ -81,6 +85,8 @@ class GradReducer:
             return
         elt = self.arena.grad.element_size()
         for region, end in ends.items():
+            if region not in self.done:
+                continue
             self.final[region] = max(self.final[region], end)
             if (self.final[region] - self.done[region]) * elt >= self.bucket:
                 self._launch(region, self.done[region], self.final[region], streams)
@@ -178,7 +184,13 @@ class PiZeroDDP(torch.nn.Module):
         ar.ensure_grad()
         if broadcast and dist.is_initialized():
             dist.broadcast(ar.data, src=0, group=group)
-        self.reducer = GradReducer(ar, region_marks(module), bucket_bytes, group)
+        # LoRA fine-tuning: the adapter region is reduced once, by finish(); a region in which nothing trains (the
+        # frozen base VLM weights, 2.3 B zeros of gradient) is left out of the all-reduce
+        skip = ()
+        if getattr(module, "has_lora", False):
+            skip = tuple(r for r in ("action", "vlm") if r in ar.region_range and not any(
+                module._requires_grad(n) for n in ar.order if ar.slots[n].region == r))
+        self.reducer = GradReducer(ar, region_marks(module), bucket_bytes, group, skip_regions=skip)
 
     @contextlib.contextmanager
     def no_sync(self):

@@ -25,6 +25,7 @@ current stream).  Layout decisions (MI355X-first):
 from __future__ import annotations
 
 import contextlib
+import functools
 import math
 import os
 import weakref
@@ -239,6 +240,90 @@ class Ada:
                     ops.colsum(dm[:, i * self.D:(i + 1) * self.D], eng.gw(n), ws, beta=beta)
 
 
+class LoraSite:
+    """The LoRA adapters of one Linear site of the training path (reference lora.py:141-211): S projections that
+    share their input and are fused along the output columns (q|k|v: 3, gate|up: 2, else 1), rank r each.
+      forward   y = x W^T + u B2^T          u = x A^T [M, S r], A = the adjacent lora_A span [S r, in];
+                                            B2 [N, S r] = the lora_B blocks packed block-diagonally (S = 1: lora_B)
+      backward  dx = dy W + v A             v = dy B2 [M, S r]
+                dA_i = s v_i^T x, dB_i = s dy_i^T u_i   (pz_lora_wgrad per projection, column slices of v / u / dy)
+    The adapter terms are summed inside the main GEMMs (pz_gemm's rank extension), so the fused RoPE / GeGLU / GELU /
+    residual epilogues stay.  The packed B2 is an engine-owned buffer rebuilt when the arena's weight version changes
+    (packed operand rather than per-column-segment addressing in the kernel: the extension stays one more K range of
+    the same pipeline, and the packing is 2-3 small copies per site and optimizer step)."""
+
+    def __init__(self, eng, wnames):
+        self.eng = eng
+        self.a = [n[: -len("weight")] + "lora_A" for n in wnames]
+        self.b = [n[: -len("weight")] + "lora_B" for n in wnames]
+        sl = eng.ar.slots
+        self.r = sl[self.a[0]].shape[0]
+        self.S = len(wnames)
+        self.outs = [sl[n].shape[0] for n in self.b]
+        self._b2 = None
+        self._b2_ver = None
+
+    def A(self):
+        return self.eng.ar.span(self.a[0], self.a[-1])
+
+    def B2(self):
+        ar = self.eng.ar
+        if self.S == 1:
+            return ar.view(self.b[0])
+        ver = self.eng.weights_version()
+        if self._b2 is None or self._b2_ver != ver or self._b2.device != ar.data.device:
+            if self._b2 is None or self._b2.device != ar.data.device:
+                self._b2 = torch.zeros(sum(self.outs), self.S * self.r, device=ar.data.device, dtype=ar.data.dtype)
+            r0 = 0
+            for i, (n, o) in enumerate(zip(self.b, self.outs)):
+                self._b2[r0:r0 + o, i * self.r:(i + 1) * self.r].copy_(ar.view(n))
+                r0 += o
+            self._b2_ver = ver
+        return self._b2
+
+    def fwd(self, x):
+        """(u, B2): the ``lora=`` operands of the site's forward GEMM; u is kept for the backward"""
+        u = torch.empty(x.shape[0], self.S * self.r, device=x.device, dtype=x.dtype)
+        ops.linear(x, self.A(), u)
+        return u, self.B2()
+
+    def bwd(self, dy):
+        """(v, A): the ``lora=`` operands of the site's input-gradient GEMM"""
+        v = torch.empty(dy.shape[0], self.S * self.r, device=dy.device, dtype=dy.dtype)
+        ops.linear_dgrad(dy, self.B2(), v)
+        return v, self.A()
+
+    def grads(self, x, u, dy, v, beta):
+        from src.model.lora import LORA_SCALING
+
+        eng, r, c0 = self.eng, self.r, 0
+        for i, o in enumerate(self.outs):
+            if eng.rg(self.a[i]):
+                ops.lora_wgrad(x, v[:, i * r:(i + 1) * r], eng.gw(self.a[i]), alpha=LORA_SCALING, beta=beta)
+            if eng.rg(self.b[i]):
+                ops.lora_wgrad(dy[:, c0:c0 + o], u[:, i * r:(i + 1) * r], eng.gw(self.b[i]), transposed=True,
+                               alpha=LORA_SCALING, beta=beta)
+            c0 += o
+
+
+def _merged_weights(fn):
+    """Inference entry point of a LoRA model: refresh the merged shadow weights and read them in place of the base"""
+
+    @functools.wraps(fn)
+    def wrap(self, *a, **k):
+        if not self.m.has_lora:
+            return fn(self, *a, **k)
+        if not torch.cuda.is_current_stream_capturing():
+            self.lora_refresh()
+        prev, self._infer = self._infer, True
+        try:
+            return fn(self, *a, **k)
+        finally:
+            self._infer = prev
+
+    return wrap
+
+
 class Group:
     """Rows of the joint sequence that share one set of mixture weights."""
 
@@ -307,6 +392,12 @@ class Engine:
         self.f8_attn = os.environ.get("PZ_FP8_ATTN", "1") == "1"
         self.f8 = None
         self.f8_version = None
+        # LoRA (lora: True): adapter sites of the training path, and the merged shadow the inference paths read
+        self._lora_sites = {}
+        self._lora_w = frozenset(n[: -len("lora_A")] + "weight" for n in self.ar.slots if n.endswith(".lora_A"))
+        self._merged = None
+        self._merged_ver = None
+        self._infer = False
         if self.d.nkv != 1:
             raise NotImplementedError("joint attention kernel path assumes MQA (num_key_value_heads=1, bridge.yaml:176)")
 
@@ -332,7 +423,45 @@ class Engine:
         return self.m._arena
 
     def w(self, name):
-        return self.ar.view(name)
+        return self.ar.view(name, self._merged if self._infer and name in self._lora_w else None)
+
+    def span(self, first, last):
+        return self.ar.span(first, last, self._merged if self._infer and first in self._lora_w else None)
+
+    # --------------------------------------------------------------- LoRA --
+    def lora(self, *wnames):
+        """LoraSite of the Linear(s) ``wnames`` (fused along N, in column order) or None without adapters"""
+        if wnames[0] not in self._lora_w:
+            return None
+        st = self._lora_sites.get(wnames)
+        if st is None:
+            st = self._lora_sites[wnames] = LoraSite(self, wnames)
+        return st
+
+    def lora_refresh(self):
+        """Merged inference weights W + s B A of every adapted Linear (the reference merges on eval(), lora.py:186-199)
+        in a shadow of the arena: one pz_gemm per Linear, C = s (B A) + resid(W).  The base weights are never written,
+        so they come back bit for bit after any train -> infer -> train sequence and state_dict() always holds the
+        unmerged tensors.  Rebuilt in place (captured graphs keep their pointers) when the weight version changed.
+        Returns True if it rebuilt."""
+        if not self._lora_w:
+            return False
+        ver = self.weights_version()
+        if self._merged is not None and self._merged_ver == ver and self._merged.device == self.ar.data.device:
+            return False
+        from src.model.lora import LORA_SCALING
+
+        if self._merged is None or self._merged.device != self.ar.data.device:
+            self._merged = torch.empty_like(self.ar.data)
+        for wn in sorted(self._lora_w):
+            W = self.ar.view(wn)
+            A = self.ar.view(wn[: -len("weight")] + "lora_A")
+            Bm = self.ar.view(wn[: -len("weight")] + "lora_B")
+            out, inn = W.shape
+            ops.gemm(out, inn, A.shape[0], Bm, A.shape[0], True, A, inn, False, self.ar.view(wn, self._merged), inn,
+                     alpha=LORA_SCALING, resid=W, ld_resid=inn)
+        self._merged_ver = ver
+        return True
 
     def gw(self, name):
         return self.ar.grad_view(name)
@@ -341,12 +470,13 @@ class Engine:
         return self.m._requires_grad(name)
 
     def qkv_w(self, p):
-        return self.ar.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight")
+        return self.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight")
 
     def gu_w(self, p):
-        return self.ar.span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight")
+        return self.span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight")
 
     # ------------------------------------------------------------ fp8 (C5) --
+    @_merged_weights
     def prepare_fp8(self):
         """fp8 e4m3 copies (per-tensor scale max|W|/448) of every inference Linear of SigLIP, the vlm
         mixture and the action expert (BASELINE.json configs[4]: fp8 attention / MLP GEMMs).  Prefill
@@ -374,7 +504,7 @@ class Engine:
                          ("w", p + "mlp.down_proj.weight")]
         f8 = {}
         for k in keys:
-            W = self.ar.span(k[1], k[2]) if k[0] == "span" else self.w(k[1])
+            W = self.span(k[1], k[2]) if k[0] == "span" else self.w(k[1])
             sc = ops.fp8_weight_scale(W)
             q = torch.empty(W.shape, device=W.device, dtype=torch.uint8)
             ops.fp8_quant_tensor(W, q, sc)
@@ -550,8 +680,15 @@ class Engine:
         Np = Nt
         layers = []
 
-        def L(x_, key, W, out, **kw):  # fp8 codes (prepare_fp8) serve inference only
-            return self.lin(x_, p + key, W, out, **kw) if save is None else ops.linear(x_, W, out, **kw)
+        def L(x_, key, W, out, site=None, **kw):  # fp8 codes (prepare_fp8) serve inference only
+            if save is None:  # (inference of a LoRA model: W is the merged weight, no adapter term)
+                return self.lin(x_, p + key, W, out, **kw)
+            u = None
+            if site is not None:  # training with adapters: + u B^T inside the GEMM; u saved for the backward
+                u, B2 = site.fwd(x_)
+                kw["lora"] = (u, B2)
+            ops.linear(x_, W, out, **kw)
+            return u
 
         for i in range(d.vL):
             p = f"{vt}encoder.layers.{i}."
@@ -566,16 +703,18 @@ class Engine:
                 ops.layernorm(x, self.w(p + "layer_norm1.weight"), self.w(p + "layer_norm1.bias"), h1, mu1, r1,
                               d.ln_eps)
             qkv = torch.empty(M, 3 * d.vH, device=dev, dtype=BF16)
-            L(h1, "self_attn.q_proj.weight", self.ar.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight"),
-              qkv, bias=self.ar.span(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias"))
+            u_qkv = L(h1, "self_attn.q_proj.weight",
+                      self.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight"), qkv,
+                      site=self.lora(*(p + f"self_attn.{k}_proj.weight" for k in "qkv")),
+                      bias=self.span(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias"))
             # fused attention (siglip.py:108-166) in place on the q|k|v rows: O and one fp32
             # log-sum-exp per (head, query) row; no [B, heads, N, N] tensor exists
             O = torch.empty(M, d.vH, device=dev, dtype=BF16)
             lse = torch.empty(B * nh, Np, device=dev, dtype=F32)
             ops.flash_fwd(ops.siglip_flash_args(qkv, O, lse, B, nh, hd, Np))
             xm = torch.empty_like(x)
-            L(O, "self_attn.out_proj.weight", self.w(p + "self_attn.out_proj.weight"), xm,
-              bias=self.w(p + "self_attn.out_proj.bias"), resid=x)
+            u_o = L(O, "self_attn.out_proj.weight", self.w(p + "self_attn.out_proj.weight"), xm,
+                    site=self.lora(p + "self_attn.out_proj.weight"), bias=self.w(p + "self_attn.out_proj.bias"), resid=x)
             if save is None and self.w8a8_in(p + "mlp.fc1.weight", M, d.vH):  # fp8: LayerNorm -> codes
                 h2 = self.norm_codes(xm, self.w(p + "layer_norm2.weight"), d.ln_eps, self.w(p + "layer_norm2.bias"))
                 mu2 = r2 = None
@@ -587,11 +726,13 @@ class Engine:
                               d.ln_eps)
             a1 = self._sig_rows(M, dev) if save is not None else None
             g1 = self._sig_rows(M, dev)
-            L(h2, "mlp.fc1.weight", self.w(p + "mlp.fc1.weight"), g1, bias=self.w(p + "mlp.fc1.bias"), epi=PZ_EPI_GELU,
-              aux=a1)
+            u_fc1 = L(h2, "mlp.fc1.weight", self.w(p + "mlp.fc1.weight"), g1, site=self.lora(p + "mlp.fc1.weight"),
+                      bias=self.w(p + "mlp.fc1.bias"), epi=PZ_EPI_GELU, aux=a1)
             xn = torch.empty_like(x)
-            L(g1, "mlp.fc2.weight", self.w(p + "mlp.fc2.weight"), xn, bias=self.w(p + "mlp.fc2.bias"), resid=xm)
+            u_fc2 = L(g1, "mlp.fc2.weight", self.w(p + "mlp.fc2.weight"), xn, site=self.lora(p + "mlp.fc2.weight"),
+                      bias=self.w(p + "mlp.fc2.bias"), resid=xm)
             if save is not None:
+                st.update(u_qkv=u_qkv, u_o=u_o, u_fc1=u_fc1, u_fc2=u_fc2)
                 st.update(h1=h1, mu1=mu1, r1=r1, qkv=qkv, lse=lse, O=O, xm=xm, h2=h2, mu2=mu2, r2=r2, a1=a1, g1=g1)
                 layers.append(st)
                 self._chk(f"siglip fwd layer {i}", h1=h1, qkv=qkv, O=O, lse=lse, xm=xm, h2=h2, g1=g1, x=xn)
@@ -601,8 +742,17 @@ class Engine:
         r = torch.empty(M, device=dev, dtype=F32)
         ops.layernorm(x, self.w(vt + "post_layernorm.weight"), self.w(vt + "post_layernorm.bias"), y, mu, r, d.ln_eps)
         img = torch.empty(M, d.proj, device=dev, dtype=BF16)
-        ops.linear(y, self.w("multi_modal_projector.linear.weight"), img, bias=self.w("multi_modal_projector.linear.bias"))
+        ps = self.lora("multi_modal_projector.linear.weight") if save is not None else None
+        u_proj = None
+        if ps is not None:
+            u_proj, B2 = ps.fwd(y)
+            ops.linear(y, self.w("multi_modal_projector.linear.weight"), img,
+                       bias=self.w("multi_modal_projector.linear.bias"), lora=(u_proj, B2))
+        else:
+            ops.linear(y, self.w("multi_modal_projector.linear.weight"), img,
+                       bias=self.w("multi_modal_projector.linear.bias"))
         if save is not None:
+            save["u_proj"] = u_proj
             save.update(layers=layers, x_last=x, y=y, mu=mu, r=r, B=B)
             self._chk("siglip fwd post-LN + projector", y=y, img=img)
         return img
@@ -637,7 +787,12 @@ class Engine:
         if self.rg(nm + "bias"):
             ops.colsum(dimg, self.gw(nm + "bias"), ws, beta=beta)
         dy = torch.empty(M, d.vH, device=dev, dtype=BF16)
-        ops.linear_dgrad(dimg, self.w(nm + "weight"), dy)
+        ps = self.lora(nm + "weight")
+        lo = None
+        if ps is not None:
+            lo = ps.bwd(dimg)
+            ps.grads(sv["y"], sv["u_proj"], dimg, lo[0], beta)
+        ops.linear_dgrad(dimg, self.w(nm + "weight"), dy, lora=lo)
         dx = torch.empty_like(dy)
         ops.layernorm_bwd(dy, sv["x_last"], self.w(vt + "post_layernorm.weight"), sv["mu"], sv["r"], dx,
                           dw_part=pw, db_part=pb, dx_part=pd)
@@ -658,14 +813,21 @@ class Engine:
             # MLP: x' = xm + fc2(gelu(fc1(ln2(xm))))
             # dgrad through fc2, then the GELU derivative at the saved pre-activation a1
             fc1b = self.rg(p + "mlp.fc1.bias")
+            s_fc2, s_fc1 = self.lora(p + "mlp.fc2.weight"), self.lora(p + "mlp.fc1.weight")
+            s_o = self.lora(p + "self_attn.out_proj.weight")
+            s_qkv = self.lora(*(p + f"self_attn.{k}_proj.weight" for k in "qkv"))
+            lo = None
+            if s_fc2 is not None:
+                lo = s_fc2.bwd(dx)
+                s_fc2.grads(st["g1"], st["u_fc2"], dx, lo[0], beta)
             if self.split_dact:  # plain dgrad GEMM, then the GELU backward (HBM-bound) in place
-                ops.linear_dgrad(dx, self.w(p + "mlp.fc2.weight"), dg)
+                ops.linear_dgrad(dx, self.w(p + "mlp.fc2.weight"), dg, lora=lo)
                 if fb and fc1b:  # + the fc1 bias gradient from the same pass
                     ops.act_bwd_colsum(dg, st["a1"], dg, PZ_EPI_GELU, ws_act, self.gw(p + "mlp.fc1.bias"), beta=beta)
                 else:
                     ops.act_bwd(dg, st["a1"], dg, None, PZ_EPI_GELU)
             else:
-                ops.linear_dgrad(dx, self.w(p + "mlp.fc2.weight"), dg, epi=PZ_EPI_DGELU, aux=st["a1"])
+                ops.linear_dgrad(dx, self.w(p + "mlp.fc2.weight"), dg, epi=PZ_EPI_DGELU, aux=st["a1"], lora=lo)
             if self.rg(p + "mlp.fc2.weight"):
                 ops.linear_wgrad(dx, st["g1"], self.gw(p + "mlp.fc2.weight"), beta=beta)
             st["g1"] = None
@@ -678,7 +840,11 @@ class Engine:
                 ops.linear_wgrad(dg, st["h2"], self.gw(p + "mlp.fc1.weight"), beta=beta)
             if fc1b and not (fb and self.split_dact):
                 ops.colsum(dg, self.gw(p + "mlp.fc1.bias"), ws, beta=beta)
-            ops.linear_dgrad(dg, self.w(p + "mlp.fc1.weight"), dh)
+            lo = None
+            if s_fc1 is not None:
+                lo = s_fc1.bwd(dg)
+                s_fc1.grads(st["h2"], st["u_fc1"], dg, lo[0], beta)
+            ops.linear_dgrad(dg, self.w(p + "mlp.fc1.weight"), dh, lora=lo)
             ops.layernorm_bwd(dh, st["xm"], self.w(p + "layer_norm2.weight"), st["mu2"], st["r2"], dxm, dres=dx,
                               dw_part=pw2, db_part=pb2, dx_part=pd2)
             self._norm_grads(p + "layer_norm2.", pw2, pb2, beta, red)
@@ -690,7 +856,11 @@ class Engine:
                     self._reduce(red, pd2, self.gw(p + "self_attn.out_proj.bias"), beta)
                 else:
                     ops.colsum(dxm, self.gw(p + "self_attn.out_proj.bias"), ws, beta=beta)
-            ops.linear_dgrad(dxm, self.w(p + "self_attn.out_proj.weight"), dO)
+            lo = None
+            if s_o is not None:
+                lo = s_o.bwd(dxm)
+                s_o.grads(st["O"], st["u_o"], dxm, lo[0], beta)
+            ops.linear_dgrad(dxm, self.w(p + "self_attn.out_proj.weight"), dO, lora=lo)
             # fused attention backward: dQ | dK | dV straight into the q|k|v gradient rows
             ops.flash_bwd(ops.siglip_flash_args(st["qkv"], st["O"], st["lse"], B, nh, hd, Np, dO=dO, delta=delta,
                                                 dqkv=dqkv))
@@ -704,7 +874,11 @@ class Engine:
                                          beta=beta)
             if all(self.rg(p + f"self_attn.{k}_proj.bias") for k in "qkv"):
                 ops.colsum(dqkv, self.ar.grad_span(qn + "bias", vn + "bias"), ws, beta=beta)
-            ops.linear_dgrad(dqkv, self.qkv_siglip(p), dh)
+            lo = None
+            if s_qkv is not None:
+                lo = s_qkv.bwd(dqkv)
+                s_qkv.grads(st["h1"], st["u_qkv"], dqkv, lo[0], beta)
+            ops.linear_dgrad(dqkv, self.qkv_siglip(p), dh, lora=lo)
             dxn = torch.empty_like(dx)
             ops.layernorm_bwd(dh, st["x"], self.w(p + "layer_norm1.weight"), st["mu1"], st["r1"], dxn, dres=dxm,
                               dw_part=pw, db_part=pb, dx_part=pdn)
@@ -731,7 +905,7 @@ class Engine:
         self._notify("vision", -1)
 
     def qkv_siglip(self, p):
-        return self.ar.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight")
+        return self.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight")
 
     def _norm_grads(self, prefix, pw, pb, beta, red=None):
         if pw is not None and self.rg(prefix + "weight"):
@@ -888,14 +1062,16 @@ class Engine:
         # q|k|v projection + RoPE + joint scatter: one 8-phase GEMM whose epilogue rotates and writes
         # Q / K / V (N1: no [M, 2560] qkv tensor, no split launch); rows too few for the 8-phase
         # kernel (the action expert's 320) take GEMM + qkv_rope_split (same bits)
+        site = self.lora(*(p + f"self_attn.{k}_proj.weight" for k in "qkv"))
+        lo = site.fwd(h) if site is not None else None
         if not (self.fuse_qkv_rope and ops.gemm_qkv_rope(h, self.qkv_w(p), pos[g.pos_key], self.rope(g.theta),
-                                                         Qj, Kj, Vj, g.T, nh, hd, L, g.off, Lp, g.off)):
+                                                         Qj, Kj, Vj, g.T, nh, hd, L, g.off, Lp, g.off, lora=lo)):
             W = (nh + 2) * hd
             qkv = torch.empty(M, W, device=dev, dtype=BF16)
-            ops.linear(h, self.qkv_w(p), qkv)
+            ops.linear(h, self.qkv_w(p), qkv, lora=lo)
             ops.qkv_rope_split(qkv, pos[g.pos_key], self.rope(g.theta), Qj, Kj, Vj, B, g.T, nh, 1, hd, L,
                                g.off, Lp, g.off)
-        st["g"][g.name] = {"x": x, "h": h, "r": r}
+        st["g"][g.name] = {"x": x, "h": h, "r": r, "u_qkv": lo[0] if lo else None}
 
     def _post_attn_ada(self, A, g, l, X, gs, Os, dev, keep=True):
         """_post_attn_train of an adaLN group: AdaptiveRMSNorm after the attention; adaLN-Zero gates both branch
@@ -940,16 +1116,23 @@ class Engine:
         M = x.shape[0]
         O = Os[g.name]
         xm = torch.empty_like(x)
-        ops.linear(O, self.w(p + "self_attn.o_proj.weight"), xm, resid=x)
+        s_o = self.lora(p + "self_attn.o_proj.weight")
+        s_gu = self.lora(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight")
+        s_dn = self.lora(p + "mlp.down_proj.weight")
+        lo_o = s_o.fwd(O) if s_o is not None else None
+        ops.linear(O, self.w(p + "self_attn.o_proj.weight"), xm, resid=x, lora=lo_o)
         h2 = torch.empty_like(x)
         r2 = torch.empty(M, device=dev, dtype=F32)
         ops.rmsnorm(xm, self.w(p + "post_attention_layernorm.weight"), h2, r2, d.rms_eps)
         gu = torch.empty(M, 2 * g.inter, device=dev, dtype=BF16)
         hm = torch.empty(M, g.inter, device=dev, dtype=BF16)
-        ops.linear(h2, self.gu_w(p), hm, epi=PZ_EPI_GEGLU, aux=gu)
+        lo_gu = s_gu.fwd(h2) if s_gu is not None else None
+        ops.linear(h2, self.gu_w(p), hm, epi=PZ_EPI_GEGLU, aux=gu, lora=lo_gu)
         xn = torch.empty_like(x)
-        ops.linear(hm, self.w(p + "mlp.down_proj.weight"), xn, resid=xm)
-        gs.update(O=O, xm=xm, h2=h2, r2=r2, gu=gu, hm=hm, skip=False)
+        lo_dn = s_dn.fwd(hm) if s_dn is not None else None
+        ops.linear(hm, self.w(p + "mlp.down_proj.weight"), xn, resid=xm, lora=lo_dn)
+        gs.update(O=O, xm=xm, h2=h2, r2=r2, gu=gu, hm=hm, skip=False, u_o=lo_o[0] if lo_o else None,
+                  u_gu=lo_gu[0] if lo_gu else None, u_dn=lo_dn[0] if lo_dn else None)
         X[g.name] = xn
 
     def _joint_layers_train(self, groups, X, pos, cnt, B, save):
@@ -1064,13 +1247,20 @@ class Engine:
         # dgrad through down_proj with the GeGLU derivative fused into its epilogue:
         # gu (saved g|u) <- d(gate|up) in place; hm (saved GeGLU output) feeds the down_proj wgrad
         gu = gs["gu"]
+        s_o = self.lora(p + "self_attn.o_proj.weight")
+        s_gu = self.lora(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight")
+        s_dn = self.lora(p + "mlp.down_proj.weight")
+        lo = None
+        if s_dn is not None:
+            lo = s_dn.bwd(dx)
+            s_dn.grads(gs["hm"], gs["u_dn"], dx, lo[0], beta)
         if self.split_dgeglu:  # plain dgrad GEMM, then the HBM-bound GeGLU backward in place on gu
             dh = torch.empty(M, g.inter, device=dev, dtype=BF16)
-            ops.linear_dgrad(dx, self.w(p + "mlp.down_proj.weight"), dh)
+            ops.linear_dgrad(dx, self.w(p + "mlp.down_proj.weight"), dh, lora=lo)
             ops.geglu_bwd(dh, gu, gu, None, M, g.inter)
             del dh
         else:
-            ops.linear_dgrad(dx, self.w(p + "mlp.down_proj.weight"), gu, epi=PZ_EPI_DGEGLU, aux=gu)
+            ops.linear_dgrad(dx, self.w(p + "mlp.down_proj.weight"), gu, epi=PZ_EPI_DGEGLU, aux=gu, lora=lo)
         if self.rg(p + "mlp.down_proj.weight"):
             ops.linear_wgrad(dx, gs["hm"], self.gw(p + "mlp.down_proj.weight"), beta=beta)
         gs["hm"] = None
@@ -1078,7 +1268,11 @@ class Engine:
             ops.linear_wgrad(gu, gs["h2"], self.ar.grad_span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"),
                              beta=beta)
         dh2 = torch.empty(M, g.hid, device=dev, dtype=BF16)
-        ops.linear_dgrad(gu, self.gu_w(p), dh2)
+        lo = None
+        if s_gu is not None:
+            lo = s_gu.bwd(gu)
+            s_gu.grads(gs["h2"], gs["u_gu"], gu, lo[0], beta)
+        ops.linear_dgrad(gu, self.gu_w(p), dh2, lora=lo)
         dxm = torch.empty_like(dx)
         if A is not None:
             A.norm_bwd(dh2, gs["xm"], gs["r2"], l, "post_", g.T, dxm, dres=dres)
@@ -1094,7 +1288,11 @@ class Engine:
         if self.rg(p + "self_attn.o_proj.weight"):
             ops.linear_wgrad(dyo, gs["O"], self.gw(p + "self_attn.o_proj.weight"), beta=beta)
         o = torch.empty(M, nh * hd, device=dev, dtype=BF16)
-        ops.linear_dgrad(dyo, self.w(p + "self_attn.o_proj.weight"), o)
+        lo = None
+        if s_o is not None:
+            lo = s_o.bwd(dyo)
+            s_o.grads(gs["O"], gs["u_o"], dyo, lo[0], beta)
+        ops.linear_dgrad(dyo, self.w(p + "self_attn.o_proj.weight"), o, lora=lo)
         dO[g.name] = o
         dXm[g.name] = dxm
 
@@ -1109,7 +1307,14 @@ class Engine:
                                B, g.T, nh, 1, hd, L, g.off, Lp, g.off)
         names = [p + f"self_attn.{k}_proj.weight" for k in "qkv"]
         rgs = [self.rg(n) for n in names]
-        if gs.get("skip"):
+        site = self.lora(*names)
+        lo = None
+        if site is not None:
+            # adapters: v = dqkv B2 over all three projections (a skipped layer's dQ columns are exactly zero, so its
+            # q adapter gets the zero gradient the reference gives it) and the general input gradient below
+            lo = site.bwd(dqkv)
+            site.grads(gs["h"], gs["u_qkv"], dqkv, lo[0], beta)
+        if gs.get("skip") and site is None:
             # last vlm layer: its query rows feed nothing (the post-attention block is skipped), so dQ = 0 exactly --
             # the q_proj gradient is zero (written as such, not computed: pizero.py:231's frozen v_proj and the zero
             # q_proj grad) and only the k|v columns enter the weight / input gradients
@@ -1119,7 +1324,7 @@ class Engine:
                 if rgk:
                     ops.linear_wgrad(dqkv[:, c0:c1], gs["h"], self.gw(n), beta=beta)
             dh = torch.empty(M, g.hid, device=dev, dtype=BF16)
-            ops.linear_dgrad(dqkv[:, nh * hd:], self.ar.span(names[1], names[2]), dh)
+            ops.linear_dgrad(dqkv[:, nh * hd:], self.span(names[1], names[2]), dh)
         else:
             if all(rgs):
                 ops.linear_wgrad(dqkv, gs["h"], self.ar.grad_span(names[0], names[2]), beta=beta)
@@ -1131,7 +1336,7 @@ class Engine:
                     if rgk:
                         ops.linear_wgrad(dqkv[:, c0:c1], gs["h"], self.gw(n), beta=beta)
             dh = torch.empty(M, g.hid, device=dev, dtype=BF16)
-            ops.linear_dgrad(dqkv, self.qkv_w(p), dh)
+            ops.linear_dgrad(dqkv, self.qkv_w(p), dh, lora=lo)
         dxn = torch.empty(M, g.hid, device=dev, dtype=BF16)
         if A is not None:
             A.norm_bwd(dh, x, gs["r"], l, "in_", g.T, dxn, dres=dXm.get(g.name))
@@ -1493,6 +1698,7 @@ class Engine:
         ops.copy_rows(pe, d.aH, 0, Xp, d.aH, 0, 1, B * d.C, d.aH, scale=math.sqrt(d.aH))
         return Xp
 
+    @_merged_weights
     def prefill(self, ids, pix, cnt, vpos, ppos, proprios, kcache, vcache, with_proprio=True):
         """pizero.py:430-451: SigLIP + prefix pass over {vlm, proprio}; writes post-RoPE K/V caches.
         with_proprio False (the adaLN expert, whose proprio rows depend on t): the vlm mixture alone -- its rows
@@ -1544,7 +1750,7 @@ class Engine:
                 ops.rmsnorm(x, self.w(p + "input_layernorm.weight"), h, None, d.rms_eps)
                 if last:  # only K/V are consumed downstream (pizero.py:451, skipped post-attn)
                     kv = torch.empty(M, 2 * hd, device=dev, dtype=BF16)
-                    ops.linear(h, self.ar.span(p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"), kv)
+                    ops.linear(h, self.span(p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"), kv)
                     qkv = torch.empty(M, (nh + 2) * hd, device=dev, dtype=BF16)
                     ops.copy_rows(kv, 2 * hd, 0, qkv[:, nh * hd:], (nh + 2) * hd, 0, 1, M, 2 * hd)
                     ops.qkv_rope_split(qkv, pos[g.pos_key], self.rope(g.theta), None, Kj, Vj, B, g.T, nh, 1, hd, L1,
@@ -1586,6 +1792,7 @@ class Engine:
         return kcache, vcache
 
     # ========================================================= text generation ==
+    @_merged_weights
     def text_forward(self, ids, pix, pos, kc, vc, start, n_img, maxpos):
         """PiZero.infer_text (pizero.py:559-593): the vlm mixture alone through all layers (cache_mode
         "append", no last-layer skip, the all-zeros text mask of pizero.py:336-365 -> no masking), the
@@ -1641,7 +1848,7 @@ class Engine:
     def _kv_only_gemv(self, x, p, pos, g, Kj, Vj, L1, Lp):
         """last prefill layer, few rows: only the k|v projection (+RoPE on k) is consumed"""
         d = self.d
-        ops.gemv_qkv_rope(x, self.ar.span(p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"), pos,
+        ops.gemv_qkv_rope(x, self.span(p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"), pos,
                           self.rope(g.theta), None, Kj, Vj, g.T, 0, d.hd, L1, g.off, Lp, g.off,
                           norm=(self.w(p + "input_layernorm.weight"), d.rms_eps))
 
@@ -1712,6 +1919,7 @@ class Engine:
         ops.linear(hm, self.w(p + "mlp.down_proj.weight"), xn, resid=xm)
         return xn
 
+    @_merged_weights
     def denoise_step(self, action, t, apos, cnt, kcache, vcache, B):
         """One Euler step of pizero.py:461-481 against the cached vlm+proprio K/V."""
         d = self.d
@@ -1797,6 +2005,7 @@ class Engine:
         ops.small_linear(y, self.w("action_decoder.weight"), v[:, : d.A], bias=self.w("action_decoder.bias"))
         ops.euler_step(action, v, 8, d.H * 8, t, B, d.H, d.A, 1.0 / d.steps)
 
+    @_merged_weights
     def denoise_step_ada(self, action, t, Xp, pos, cnt, kcache, vcache, B):
         """One Euler step of the adaLN expert with the semantics of the reference's infer_action_naive
         (pizero.py:492-557): the proprio AND action rows of every sample run again with cond(t) -- the proprio K/V
@@ -1868,6 +2077,7 @@ class Engine:
         ops.small_linear(y, self.w("action_decoder.weight"), v[:, : d.A], bias=self.w("action_decoder.bias"))
         ops.euler_step(action, v[aoff:], 8, Tg * 8, t, B, d.H, d.A, 1.0 / d.steps)
 
+    @_merged_weights
     def infer_action(self, ids, pix, cnt, vpos, ppos, apos, proprios, noise, kcache, vcache, clip=True):
         """pizero.py:416-490.  With an adaLN expert both this and PiZero.infer_action_naive compute the naive
         semantics (pizero.py:492-557): the reference's cached infer_action raises AttributeError there ('NoneType'

@@ -57,6 +57,7 @@ class InferenceGraph:
         # re-quantise stale fp8 codes first, so the codes recorded here are the ones the captured launches read
         # (the warm-up's infer_action would otherwise replace them and force a needless re-capture)
         e = self.m._engine()
+        e.lora_refresh()  # LoRA: the merged shadow weights the captured launches read (never rebuilt inside a capture)
         e.fp8_refresh()
         self._f8 = e.f8
         side = torch.cuda.Stream()
@@ -78,6 +79,7 @@ class InferenceGraph:
         # since the capture re-quantises them (Engine.fp8_refresh) and re-captures the graph
         e = self.m._engine()
         e.derived_refresh()  # in place: the captured launches keep their pointers
+        e.lora_refresh()  # LoRA: merged weights rebuilt in place after an optimizer step / checkpoint load
         if e.f8 is not self._f8 or e.fp8_refresh():
             self.capture()
         self.graph.replay()

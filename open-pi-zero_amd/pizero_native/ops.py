@@ -58,19 +58,20 @@ def set_probe(pred):
 
 def gemm(M, N, K, A, lda, a_kc, B, ldb, b_kc, Cm, ldc, *, epi=PZ_EPI_NONE, alpha=1.0, beta=False,
          bias=None, resid=None, ld_resid=0, aux=None, ld_aux=0, geglu_inter=0, batch=1, batch_inner=1,
-         sA=(0, 0), sB=(0, 0), sC=(0, 0), sR=(0, 0), norm=None):
+         sA=(0, 0), sB=(0, 0), sC=(0, 0), sR=(0, 0), norm=None, ext=None):
     """Raw GEMM: see pz_gemm_args in include/pz_abi.h.  Element strides.  norm = (w, eps): fused
-    Gemma RMSNorm of the A rows (few-row path only)."""
+    Gemma RMSNorm of the A rows (few-row path only).  ext = (A2, lda2, B2, ldb2, K2): the rank extension
+    (a second operand pair with the k-contiguity of A / B, summed before the epilogue)."""
     if _PROBE is not None and _PROBE[0](M, N, K, epi, batch):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         _gemm(M, N, K, A, lda, a_kc, B, ldb, b_kc, Cm, ldc, epi, alpha, beta, bias, resid, ld_resid, aux, ld_aux,
-              geglu_inter, batch, batch_inner, sA, sB, sC, sR, norm)
+              geglu_inter, batch, batch_inner, sA, sB, sC, sR, norm, ext)
         e1.record()
         _PROBE[1].append((e0, e1))
         return
     _gemm(M, N, K, A, lda, a_kc, B, ldb, b_kc, Cm, ldc, epi, alpha, beta, bias, resid, ld_resid, aux, ld_aux,
-          geglu_inter, batch, batch_inner, sA, sB, sC, sR, norm)
+          geglu_inter, batch, batch_inner, sA, sB, sC, sR, norm, ext)
 
 
 _WS_BYTES = 160 << 20  # split-K / split-tail fp32 partials (multi-round tails: up to 640 x 256 KiB)
@@ -131,41 +132,64 @@ def _args(M, N, K, A, lda, a_kc, B, ldb, b_kc, Cm, ldc, epi, alpha, beta, bias, 
 
 
 def _gemm(M, N, K, A, lda, a_kc, B, ldb, b_kc, Cm, ldc, epi, alpha, beta, bias, resid, ld_resid, aux, ld_aux,
-          geglu_inter, batch, batch_inner, sA, sB, sC, sR, norm=None):
+          geglu_inter, batch, batch_inner, sA, sB, sC, sR, norm=None, ext=None):
     ws = workspace(Cm.device) if batch == 1 else None
     a = _args(M, N, K, A, lda, a_kc, B, ldb, b_kc, Cm, ldc, epi, alpha, beta, bias, resid, ld_resid, aux, ld_aux,
               geglu_inter, batch, batch_inner, sA, sB, sC, sR, ws, norm)
+    if ext is not None:
+        a.A2, a.lda2, a.B2, a.ldb2, a.K2 = _p(ext[0]), int(ext[1]), _p(ext[2]), int(ext[3]), int(ext[4])
     call("pz_gemm", C.byref(a), _st())
 
 
 def gemm_kernel_name(M, N, K, *, a_kc=True, b_kc=True, epi=PZ_EPI_NONE, geglu_inter=0, batch=1, c_fp32=False,
-                     workspace_bytes=_WS_BYTES, fp8_mode=0):
+                     workspace_bytes=_WS_BYTES, fp8_mode=0, K2=0):
     """Name of the kernel pz_gemm dispatches for this problem (bench / profile labels; fp8_mode 1 = W8A8 with row
-    scales, 2 = W8A16, K in codes)."""
+    scales, 2 = W8A16, K in codes; K2: depth of the rank extension)."""
     a = GemmArgs()
     a.M, a.N, a.K = int(M), int(N), int(K)
     a.a_kcontig, a.b_kcontig, a.c_fp32 = int(a_kc), int(b_kc), int(c_fp32)
     a.batch, a.batch_inner, a.epilogue, a.geglu_inter = int(batch), 1, int(epi), int(geglu_inter)
     a.workspace, a.ws_bytes = (256 if workspace_bytes else None), int(workspace_bytes)
     a.fp8_mode = int(fp8_mode)
+    a.K2 = int(K2)
     if fp8_mode == 1:
         a.a_row_scale, a.lda, a.ldb = 256, int(K), int(K)
     return lib().pz_gemm_kernel_name(C.byref(a)).decode()
 
 
-def linear(x, W, out, *, bias=None, resid=None, epi=PZ_EPI_NONE, aux=None, alpha=1.0, beta=False, norm=None):
+def linear(x, W, out, *, bias=None, resid=None, epi=PZ_EPI_NONE, aux=None, alpha=1.0, beta=False, norm=None,
+           lora=None):
     """out[M,N] = epi(x[M,K] @ W[N,K]^T): nn.Linear forward (x, out may be row-strided 2-D views).
-    norm = (w, eps): x is first Gemma-RMS-normalised inside the GEMM (M <= 16 rows only)."""
+    norm = (w, eps): x is first Gemma-RMS-normalised inside the GEMM (M <= 16 rows only).
+    lora = (u [M, R], Bm [N, R]): out = epi(x W^T + u Bm^T), the adapter term summed inside the GEMM."""
     M, K = x.shape
     N = W.shape[0]
+    ext = None if lora is None else (lora[0], lora[0].stride(0), lora[1], lora[1].stride(0), lora[0].shape[1])
     if epi == PZ_EPI_GEGLU:
         I = N // 2
         gemm(M, N, K, x, x.stride(0), True, W, W.stride(0), True, out, out.stride(0), epi=epi,
-             aux=aux, ld_aux=0 if aux is None else aux.stride(0), geglu_inter=I, alpha=alpha, norm=norm)
+             aux=aux, ld_aux=0 if aux is None else aux.stride(0), geglu_inter=I, alpha=alpha, norm=norm, ext=ext)
         return out
     gemm(M, N, K, x, x.stride(0), True, W, W.stride(0), True, out, out.stride(0), epi=epi, alpha=alpha,
          beta=beta, bias=bias, resid=resid, ld_resid=0 if resid is None else resid.stride(0), aux=aux,
-         ld_aux=0 if aux is None else aux.stride(0), norm=norm)
+         ld_aux=0 if aux is None else aux.stride(0), norm=norm, ext=ext)
+    return out
+
+
+def lora_wgrad_ws_bytes(M, D, R):
+    """bytes of fp32 workspace pz_lora_wgrad needs for Q [M, D] and P [M, R]"""
+    return int(lib().pz_lora_wgrad_ws_bytes(int(M), int(D), int(R)))
+
+
+def lora_wgrad(Q, P, out, *, transposed=False, alpha=1.0, beta=False, ws=None):
+    """out[R, D] (+)= alpha P[M, R]^T Q[M, D] (transposed: out[D, R]); Q / P may be column slices of wider
+    row-major tensors.  Deterministic fixed-order reduction over M through the fp32 workspace ws (default: the
+    GEMM workspace of the current stream slot)."""
+    M, D = Q.shape
+    R = P.shape[1]
+    ws = workspace(Q.device) if ws is None else ws
+    call("pz_lora_wgrad", _p(Q), Q.stride(0), _p(P), P.stride(0), _p(out), out.stride(0), M, D, R, int(transposed),
+         float(alpha), int(bool(beta)), _p(ws), ws.numel() * ws.element_size(), _st())
     return out
 
 
@@ -244,17 +268,19 @@ def rows_w8a16_ok(M, K, ncols):
     return 64 < M <= maxm and K % 64 == 0 and (os.environ.get("PZ_GEMM_ROWS") == "1" or (K <= 2048 and ncols <= 4096))
 
 
-def linear_dgrad(dy, W, dx, *, beta=False, resid=None, epi=PZ_EPI_NONE, aux=None):
+def linear_dgrad(dy, W, dx, *, beta=False, resid=None, epi=PZ_EPI_NONE, aux=None, lora=None):
     """dx[M,K] (+)= dy[M,N] @ W[N,K] (+ resid).
 
     Backward epilogues (aux read): PZ_EPI_DGELU / PZ_EPI_DSILU multiply by the activation
     derivative at the saved pre-activation aux[M,K]; PZ_EPI_DGEGLU takes aux = saved [g | u]
-    ([M, 2K]) and writes d(gate|up) into dx[M, 2K] (dx may be aux itself)."""
+    ([M, 2K]) and writes d(gate|up) into dx[M, 2K] (dx may be aux itself).
+    lora = (v [M, R], Am [R, K]): dx = epi(dy W + v Am), the adapter's input gradient summed inside the GEMM."""
     M, N = dy.shape
     K = W.shape[1]
+    ext = None if lora is None else (lora[0], lora[0].stride(0), lora[1], lora[1].stride(0), lora[0].shape[1])
     gemm(M, K, N, dy, dy.stride(0), True, W, W.stride(0), False, dx, dx.stride(0), beta=beta,
          resid=resid, ld_resid=0 if resid is None else resid.stride(0), epi=epi, aux=aux,
-         ld_aux=0 if aux is None else aux.stride(0), geglu_inter=K if epi == PZ_EPI_DGEGLU else 0)
+         ld_aux=0 if aux is None else aux.stride(0), geglu_inter=K if epi == PZ_EPI_DGEGLU else 0, ext=ext)
     return dx
 
 
@@ -454,7 +480,8 @@ def gemv_qkv_rope(x, W, pos, cs, q_out, k_out, v_out, T, nh, hd, Lq, qoff, Lk, k
 PZ_ERR_UNSUPPORTED = 3  # include/pz_abi.h
 
 
-def gemm_qkv_rope(x, W, pos, cs, q_out, k_out, v_out, T, nh, hd, Lq, qoff, Lk, koff, norm=None, w_scale=None):
+def gemm_qkv_rope(x, W, pos, cs, q_out, k_out, v_out, T, nh, hd, Lq, qoff, Lk, koff, norm=None, w_scale=None,
+                  lora=None):
     """q|k|v projection with RoPE and the joint Q / K / V scatter fused into the GEMM's epilogue
     (pz_gemm_qkv_rope): the 8-phase kernel for many rows, the skinny-64 kernel for 16 < M <= 64 (norm = (w, eps):
     fused Gemma RMSNorm; w_scale: W is e4m3 codes, W8A16 -- few-row path only).  Returns False (nothing launched) when the shape takes neither --
@@ -470,6 +497,8 @@ def gemm_qkv_rope(x, W, pos, cs, q_out, k_out, v_out, T, nh, hd, Lq, qoff, Lk, k
     a.pos, a.cs = _p(pos), _p(cs)
     a.q_out, a.k_out, a.v_out = _p(q_out), _p(k_out), _p(v_out)
     a.T, a.nh, a.hd, a.Lq, a.qoff, a.Lk, a.koff = T, nh, hd, Lq, qoff, Lk, koff
+    if lora is not None:  # (u [M, R], Bm [N, R]): the adapter term summed inside the GEMM (8-phase path only)
+        a.x2, a.ldx2, a.W2, a.ldw2, a.K2 = _p(lora[0]), lora[0].stride(0), _p(lora[1]), lora[1].stride(0), lora[0].shape[1]
     rc = lib().pz_gemm_qkv_rope(C.byref(a), _st())
     if rc == PZ_ERR_UNSUPPORTED:
         return False

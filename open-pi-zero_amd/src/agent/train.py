@@ -102,6 +102,11 @@ class TrainAgent:
         self.cnt_update = 0
         self.cnt_batch = 0
         self.wandb_id = None
+        self.lora = bool(cfg_get(cfg, "lora", False))
+        if cfg_get(cfg, "quantize", False):
+            raise NotImplementedError("quantize: True (4-bit bitsandbytes) is not supported; use lora: True alone")
+        if self.lora and not cfg_get(cfg, "load_pretrained_weights", False):  # train.py:87-89
+            raise AssertionError("lora: True must be used with load_pretrained_weights: True")
         model = PiZero(cfg, use_ddp=self.multi_gpu, device=self.device, dtype=self.dtype, init="default")
         self.model = model
         resume = cfg_get(cfg, "resume_checkpoint_path")
@@ -111,6 +116,8 @@ class TrainAgent:
             model.load_pretrained_weights()
         model.tie_action_proprio_weights()
         model.freeze_unused_weights()
+        if self.lora:  # train.py:101-102
+            model.freeze_non_lora_weights_in_vlm()
         self.model_meta = PiZeroDDP(model) if self.multi_gpu else model
 
         per_dev = int(cfg_get(cfg, "per_device_batch_size"))
@@ -129,7 +136,8 @@ class TrainAgent:
         self.action_lr_scheduler = sch(self.action_optimizer, "action_lr_scheduler", cfg_get(cfg, "action_lr"))
         self.optimizers = [self.action_optimizer]
         if self.train_vlm:
-            self.vlm_optimizer = FusedAdamW(model.trainable_vlm_parameters, lr=cfg_get(cfg, "vlm_lr"),
+            vlm_params = model.lora_trainable_vlm_parameters if self.lora else model.trainable_vlm_parameters
+            self.vlm_optimizer = FusedAdamW(vlm_params, lr=cfg_get(cfg, "vlm_lr"),
                                             weight_decay=cfg_get(cfg, "vlm_weight_decay", 0.0),
                                             state_bits=self.state_bits)
             self.vlm_lr_scheduler = sch(self.vlm_optimizer, "vlm_lr_scheduler", cfg_get(cfg, "vlm_lr"))

@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
+from src.model.lora import lora_rank, make_linear
 from src.utils.config import cfg_get
 
 
@@ -33,11 +34,10 @@ class GemmaRotaryEmbedding(nn.Module):
 class GemmaMLP(nn.Module):
     def __init__(self, config, use_quantize=False, use_lora=False):
         super().__init__()
-        if use_quantize or use_lora:
-            raise NotImplementedError("QLoRA/LoRA are out of scope (SURVEY 2.1)")
+        r = lora_rank(config, use_quantize, use_lora)
         self.config = config
         self.hidden_size = cfg_get(config, "hidden_size")
         self.intermediate_size = cfg_get(config, "intermediate_size")
-        self.gate_proj = nn.Linear(self.hidden_size, self.intermediate_size, bias=False)
-        self.up_proj = nn.Linear(self.hidden_size, self.intermediate_size, bias=False)
-        self.down_proj = nn.Linear(self.intermediate_size, self.hidden_size, bias=False)
+        self.gate_proj = make_linear(self.hidden_size, self.intermediate_size, r, bias=False)
+        self.up_proj = make_linear(self.hidden_size, self.intermediate_size, r, bias=False)
+        self.down_proj = make_linear(self.intermediate_size, self.hidden_size, r, bias=False)

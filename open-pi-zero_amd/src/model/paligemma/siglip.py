@@ -16,6 +16,7 @@ from __future__ import annotations
 
 from torch import nn
 
+from src.model.lora import lora_rank, make_linear
 from src.utils.config import cfg_get
 
 
@@ -30,10 +31,9 @@ class PaliGemmaMultiModalProjector(nn.Module):
 
     def __init__(self, config, use_quantize: bool = False, use_lora: bool = False):
         super().__init__()
-        if use_quantize or use_lora:
-            raise NotImplementedError("QLoRA/LoRA are out of scope (SURVEY 2.1: lora/quantize False)")
-        self.linear = nn.Linear(cfg_get(config, "vision_config.hidden_size"),
-                                cfg_get(config, "vision_config.projection_dim"), bias=True)
+        r = lora_rank(config, use_quantize, use_lora)
+        self.linear = make_linear(cfg_get(config, "vision_config.hidden_size"),
+                                  cfg_get(config, "vision_config.projection_dim"), r, bias=True)
 
     def forward(self, image_features):
         _native_only("PaliGemmaMultiModalProjector")
@@ -70,10 +70,11 @@ class SiglipAttention(nn.Module):
         self.scale = self.head_dim ** -0.5
         self.dropout = cfg_get(config, "attention_dropout", 0.0)
         # registration order of the reference (k, v, q, out) keeps state_dict order identical
-        self.k_proj = nn.Linear(self.embed_dim, self.embed_dim)
-        self.v_proj = nn.Linear(self.embed_dim, self.embed_dim)
-        self.q_proj = nn.Linear(self.embed_dim, self.embed_dim)
-        self.out_proj = nn.Linear(self.embed_dim, self.embed_dim)
+        r = lora_rank(config, use_quantize, use_lora)
+        self.k_proj = make_linear(self.embed_dim, self.embed_dim, r)
+        self.v_proj = make_linear(self.embed_dim, self.embed_dim, r)
+        self.q_proj = make_linear(self.embed_dim, self.embed_dim, r)
+        self.out_proj = make_linear(self.embed_dim, self.embed_dim, r)
 
     def forward(self, hidden_states):
         _native_only("SiglipAttention")
@@ -85,8 +86,9 @@ class SiglipMLP(nn.Module):
     def __init__(self, config, use_quantize: bool = False, use_lora: bool = False):
         super().__init__()
         self.config = config
-        self.fc1 = nn.Linear(cfg_get(config, "hidden_size"), cfg_get(config, "intermediate_size"))
-        self.fc2 = nn.Linear(cfg_get(config, "intermediate_size"), cfg_get(config, "hidden_size"))
+        r = lora_rank(config, use_quantize, use_lora)
+        self.fc1 = make_linear(cfg_get(config, "hidden_size"), cfg_get(config, "intermediate_size"), r)
+        self.fc2 = make_linear(cfg_get(config, "intermediate_size"), cfg_get(config, "hidden_size"), r)
 
     def forward(self, hidden_states):
         _native_only("SiglipMLP")
@@ -99,9 +101,9 @@ class SiglipEncoderLayer(nn.Module):
         super().__init__()
         self.embed_dim = cfg_get(config, "hidden_size")
         eps = float(cfg_get(config, "layer_norm_eps", 1e-6))
-        self.self_attn = SiglipAttention(config)
+        self.self_attn = SiglipAttention(config, use_quantize=use_quantize, use_lora=use_lora)
         self.layer_norm1 = nn.LayerNorm(self.embed_dim, eps=eps)
-        self.mlp = SiglipMLP(config)
+        self.mlp = SiglipMLP(config, use_quantize=use_quantize, use_lora=use_lora)
         self.layer_norm2 = nn.LayerNorm(self.embed_dim, eps=eps)
 
     def forward(self, hidden_states):
@@ -112,7 +114,7 @@ class SiglipEncoder(nn.Module):
     def __init__(self, config, use_quantize: bool = False, use_lora: bool = False):
         super().__init__()
         self.config = config
-        self.layers = nn.ModuleList([SiglipEncoderLayer(config) for _ in range(cfg_get(config, "num_hidden_layers"))])
+        self.layers = nn.ModuleList([SiglipEncoderLayer(config, use_quantize=use_quantize, use_lora=use_lora) for _ in range(cfg_get(config, "num_hidden_layers"))])
 
     def forward(self, inputs_embeds):
         _native_only("SiglipEncoder")
@@ -123,7 +125,7 @@ class SiglipVisionTransformer(nn.Module):
         super().__init__()
         self.config = config
         self.embeddings = SiglipVisionEmbeddings(config)
-        self.encoder = SiglipEncoder(config)
+        self.encoder = SiglipEncoder(config, use_quantize=use_quantize, use_lora=use_lora)
         self.post_layernorm = nn.LayerNorm(cfg_get(config, "hidden_size"),
                                            eps=float(cfg_get(config, "layer_norm_eps", 1e-6)))
 
@@ -136,10 +138,9 @@ class SiglipVisionModel(nn.Module):
 
     def __init__(self, config, use_quantize: bool = False, use_lora: bool = False):
         super().__init__()
-        if use_quantize or use_lora:
-            raise NotImplementedError("QLoRA/LoRA are out of scope (SURVEY 2.1: lora/quantize False)")
+        lora_rank(config, use_quantize, use_lora)  # refuses quantize / lora_dropout > 0 before anything is built
         self.config = config
-        self.vision_model = SiglipVisionTransformer(config)
+        self.vision_model = SiglipVisionTransformer(config, use_quantize=use_quantize, use_lora=use_lora)
 
     def forward(self, pixel_values):
         _native_only("SiglipVisionModel")

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 from torch import nn
 
+from src.model.lora import lora_rank, make_linear
 from src.model.paligemma.modules import GemmaMLP, GemmaRMSNorm, GemmaRotaryEmbedding
 from src.model.vla.modules import AdaptiveLayerscale, AdaptiveRMSNorm
 from src.utils.config import cfg_get
@@ -80,8 +81,9 @@ class MixtureAttention(nn.Module):
         bias = bool(cfg_get(config, "attention_bias", False))
         if bias:
             raise NotImplementedError("attention_bias=True is not used by Pi0 (bridge.yaml:179)")
-        self.q_proj = nn.Linear(hid, self.num_heads * self.head_dim, bias=False)
-        self.k_proj = nn.Linear(hid, self.num_key_value_heads * self.head_dim, bias=False)
-        self.v_proj = nn.Linear(hid, self.num_key_value_heads * self.head_dim, bias=False)
-        self.o_proj = nn.Linear(self.num_heads * self.head_dim, hid, bias=False)
+        r = lora_rank(config, cfg_get(config, "use_quantize", False), cfg_get(config, "use_lora", False))
+        self.q_proj = make_linear(hid, self.num_heads * self.head_dim, r, bias=False)
+        self.k_proj = make_linear(hid, self.num_key_value_heads * self.head_dim, r, bias=False)
+        self.v_proj = make_linear(hid, self.num_key_value_heads * self.head_dim, r, bias=False)
+        self.o_proj = make_linear(self.num_heads * self.head_dim, hid, r, bias=False)
         self.rotary_emb = GemmaRotaryEmbedding(self.head_dim, base=cfg_get(config, "rope_theta", 10000.0))

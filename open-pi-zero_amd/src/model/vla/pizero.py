@@ -198,8 +198,46 @@ class PiZero(nn.Module, NoSyncBase):
                 out.append((p + n, "vlm"))
         out += [(vt + "embeddings.position_embedding.weight", "vlm"),
                 (vt + "embeddings.patch_embedding.weight", "vlm"), (vt + "embeddings.patch_embedding.bias", "vlm")]
+        out += self._lora_layout()
         out += [("embed_tokens.weight", "frozen")]
         return out
+
+    def _lora_layout(self):
+        """The LoRA adapters, all in one arena region ("lora") behind the VLM weights, in backward-completion order.
+        A (possibly fused) site's lora_A tensors are adjacent, then its lora_B tensors: the q|k|v (gate|up) A span
+        is the stacked [S r, in] operand of one u = x A^T GEMM and of the input-gradient extension, the B span the
+        stacked [N, r] rows the engine packs block-diagonally.  The base weights keep their places, so the fused
+        q|k|v and gate|up weight spans are unchanged; the trainable parameters of a LoRA run form one contiguous
+        run per optimizer group (minus the last vlm layer's frozen adapters) and one data-parallel bucket."""
+        from src.model.lora import LoRALinear
+
+        out = []
+
+        def site(prefix, projs):
+            mod, _ = _resolve(self, prefix + projs[0] + ".weight")
+            if isinstance(mod, LoRALinear):
+                out.extend((f"{prefix}{pr}.lora_A", "lora") for pr in projs)
+                out.extend((f"{prefix}{pr}.lora_B", "lora") for pr in projs)
+
+        nL = self.joint_model.num_hidden_layers
+        for l in reversed(range(nL)):
+            p = f"joint_model.mixtures.vlm.layers.{l}."
+            site(p + "mlp.", ["down_proj"])
+            site(p + "mlp.", ["gate_proj", "up_proj"])
+            site(p + "self_attn.", ["o_proj"])
+            site(p + "self_attn.", ["q_proj", "k_proj", "v_proj"])
+        site("multi_modal_projector.", ["linear"])
+        vt = "vision_tower.vision_model.encoder.layers."
+        for i in reversed(range(len(self.vision_tower.vision_model.encoder.layers))):
+            site(f"{vt}{i}.mlp.", ["fc2"])
+            site(f"{vt}{i}.mlp.", ["fc1"])
+            site(f"{vt}{i}.self_attn.", ["out_proj"])
+            site(f"{vt}{i}.self_attn.", ["q_proj", "k_proj", "v_proj"])
+        return out
+
+    @property
+    def has_lora(self):
+        return "lora" in self._arena.region_range
 
     def _build_arena(self, device, dtype, init="keep"):
         from pizero_native.arena import Arena
@@ -227,6 +265,9 @@ class PiZero(nn.Module, NoSyncBase):
         g = torch.Generator(device="cpu").manual_seed(0)
         for name in self._arena.order:
             v = self._arena.view(name)
+            if name.endswith(".lora_B"):  # lora.py:176-179: B = 0, A = kaiming_uniform(a=sqrt(5)) = U(+-1/sqrt(in)) (below)
+                v.zero_()
+                continue
             if "to_adaln_zero_gamma" in name:  # AdaptiveLayerscale: weight 0, bias -2 (vla/modules.py:107-109)
                 v.fill_(0.0 if name.endswith("weight") else -2.0)
                 continue
@@ -274,8 +315,8 @@ class PiZero(nn.Module, NoSyncBase):
         return self._param(name).requires_grad
 
     def _vlm_needs_grad(self):
-        a, z = self._arena.region_range["vlm"]
-        return any(self._param(n).requires_grad for n in self._arena.order if self._arena.slots[n].region == "vlm")
+        return any(self._param(n).requires_grad for n in self._arena.order
+                   if self._arena.slots[n].region in ("vlm", "lora"))
 
     def _trainable_names(self):
         return [n for n in self._arena.order if self._param(n).requires_grad]
@@ -338,7 +379,15 @@ class PiZero(nn.Module, NoSyncBase):
 
     @property
     def lora_trainable_vlm_parameters(self):
-        return []  # LoRA out of scope (lora: False)
+        """pizero.py:131-142: every lora_ tensor of SigLIP and the projector, and the used ones of the vlm mixture"""
+        return ([p for n, p in self.vision_tower.named_parameters() if "lora_" in n]
+                + [p for n, p in self.multi_modal_projector.named_parameters() if "lora_" in n]
+                + self.trainable_lora_gemma_parameters)
+
+    @property
+    def trainable_lora_gemma_parameters(self):
+        return [p for n, p in self.joint_model.mixtures["vlm"].named_parameters()
+                if not self._check_gemma_unused_parameter_by_name(n) and "lora_" in n]
 
     @property
     def trainable_gemma_parameters(self):
@@ -377,7 +426,15 @@ class PiZero(nn.Module, NoSyncBase):
         log.info("Loaded pre-trained PaliGemma weights (%d tensors, %d keys not in checkpoint)", len(sd), len(missing))
 
     def freeze_non_lora_weights_in_vlm(self):
-        raise NotImplementedError("LoRA is out of scope (SURVEY 2.1)")
+        """pizero.py:236-249: only the lora_ tensors of SigLIP, the projector and the vlm mixture stay trainable (every
+        bias frozen); the last vlm layer's unused tensors are left as freeze_unused_weights set them."""
+        for name, param in self.vision_tower.named_parameters():
+            param.requires_grad = "lora_" in name
+        for name, param in self.multi_modal_projector.named_parameters():
+            param.requires_grad = "lora_" in name
+        for name, param in self.joint_model.mixtures["vlm"].named_parameters():
+            if not self._check_gemma_unused_parameter_by_name(name):
+                param.requires_grad = "lora_" in name
 
     def freeze_unused_weights(self):
         self.embed_tokens.weight.requires_grad = False
