@@ -622,6 +622,11 @@ def flash_bwd(a):
     call("pz_flash_bwd", C.byref(a), _st())
 
 
+def flash_bwd_prep(a):
+    """a.delta [Z*H, nq] = rowsum(dO * O) over the output groups (a.g_o / a.g_do); pz_flash_bwd_prep."""
+    call("pz_flash_bwd_prep", C.byref(a), _st())
+
+
 def siglip_flash_args(qkv, O, lse, B, nh, hd, N, dO=None, delta=None, dqkv=None):
     """SigLIP attention in place on the fused q|k|v projection rows [B*N, 3*nh*hd]; O [B*N, nh*hd]."""
     W = qkv.stride(0)
