@@ -467,6 +467,16 @@ int pz_lora_wgrad(const void* Q, int64_t ldq, const void* P, int64_t ldp, void* 
                   int64_t D, int64_t R, int32_t transposed, float alpha, int32_t beta, void* ws, int64_t ws_bytes,
                   void* stream);
 
+/* Weight averaging over flat bf16 buffers (EMA / SWA: model_averaging.py, torch.optim.swa_utils.AveragedModel;
+ * csrc/pz_avg.hip).  Entry points added under ABI 22 (no existing signature changed).
+ *   pz_avg_lerp: avg[i] <- bf16_rne(|w| < 0.5 ? fma(w, d, a) : fma(-d, 1 - w, x)), a = avg[i], x = p[i], d = x - a
+ *                in fp32 -- torch.lerp(avg, p, w) for bf16, bit for bit.
+ *   pz_avg_swap: exchanges a[0..n) and b[0..n) in place (no temporary).
+ * Any n >= 1; both pointers 16-byte aligned, the two ranges disjoint (else PZ_ERR_INVALID_ARG before any launch).
+ * Deterministic, no atomics. */
+int pz_avg_lerp(void* avg, const void* p, int64_t n, float w, void* stream);
+int pz_avg_swap(void* a, void* b, int64_t n, void* stream);
+
 /* test instrument: fill every CU's LDS with `word` (0xffffffff = NaN) on `stream`, so the next kernel's reads of
  * LDS it did not write return NaN (tests/test_train_loop_gpu.py; _lib.call runs it before every launch under
  * PZ_POISON_LDS=1).  Not on any product path. */

@@ -185,6 +185,8 @@ SIGNATURES = {
     "pz_adaln_gate_bwd": [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, vp],
     "pz_lora_wgrad_ws_bytes": [i64, i64, i64],
     "pz_lora_wgrad": [vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, f32, i32, vp, i64, vp],
+    "pz_avg_lerp": [vp, vp, i64, f32, vp],
+    "pz_avg_swap": [vp, vp, i64, vp],
     "pz_debug_poison_lds": [C.c_uint32, vp],
     "pz_debug_spin": [i64, i64, vp],
     "pz_last_error": [],

@@ -775,6 +775,21 @@ def cast_to_bf16(x, y):
     call("pz_cast_f32_bf16", _p(x), _p(y), x.numel(), _st())
 
 
+def avg_lerp(avg, p, w):
+    """avg <- torch.lerp(avg, p, w) over two flat contiguous bf16 tensors of equal length, in place, bit-identical
+    to torch's bf16 lerp (weight averaging: averaging.FlatAverage)."""
+    assert avg.dtype == BF16 and p.dtype == BF16 and avg.numel() == p.numel()
+    assert avg.is_contiguous() and p.is_contiguous()
+    call("pz_avg_lerp", _p(avg), _p(p), avg.numel(), float(w), _st())
+
+
+def avg_swap(a, b):
+    """exchange the contents of two flat contiguous bf16 tensors of equal length, in place"""
+    assert a.dtype == BF16 and b.dtype == BF16 and a.numel() == b.numel()
+    assert a.is_contiguous() and b.is_contiguous()
+    call("pz_avg_swap", _p(a), _p(b), a.numel(), _st())
+
+
 def debug_poison_lds(word=0xFFFFFFFF):
     """Test instrument: fill every CU's LDS with ``word`` (0xffffffff = NaN) on the current stream."""
     call("pz_debug_poison_lds", C.c_uint32(int(word) & 0xFFFFFFFF), _st())

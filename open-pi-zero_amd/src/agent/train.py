@@ -8,7 +8,11 @@ Same structure and semantics as shroglck/open-pi-zero's TrainAgent:
   * flow-matching time sampling (beta / uniform), per-batch preprocessing into
     the 9 forward kwargs (pizero.py:607-618);
   * checkpoints with the reference's keys (cnt_update, cnt_batch, model,
-    action_optimizer, vlm_optimizer, *_lr_scheduler, wandb_id, n_averaged).
+    action_optimizer, vlm_optimizer, *_lr_scheduler, wandb_id, n_averaged);
+  * EMA / SWA weight averaging (src.agent.model_averaging.ModelAveraging, train.py:268-269,389-393), in-training
+    validation on the averaged weights (train.py:413-459) and the averaged weights as the checkpoint's "model"
+    (train.py:497-529).  An extension: with averaging active the checkpoint also holds the live weights
+    ("model_train"), so the average can be resumed exactly (the reference cannot resume one).
 MI355X-native pieces: pizero_native.ddp.PiZeroDDP (RCCL bucketed all-reduce
 overlapped with backward), pizero_native.optim.FusedAdamW (flat fused AdamW; by default
 with the reference's blockwise 8-bit state, ``optimizer_state_bits: 8`` -- the algorithm of
@@ -75,9 +79,10 @@ class SyntheticBridgeDataset(torch.utils.data.IterableDataset):
 
 
 class TrainAgent:
-    def __init__(self, cfg, dataset=None):
+    def __init__(self, cfg, dataset=None, val_dataset=None):
         from pizero_native.ddp import PiZeroDDP
         from pizero_native.optim import FusedAdamW
+        from src.agent.model_averaging import ModelAveraging
         from src.model.vla.pizero import PiZero
         from src.utils.optim import CosineAnnealingWarmupRestarts
 
@@ -96,6 +101,7 @@ class TrainAgent:
         self.max_grad_norm = float(cfg_get(cfg, "max_grad_norm", 1.0))
         self.log_freq = int(cfg_get(cfg, "log_freq", 16))
         self.save_model_freq = int(cfg_get(cfg, "save_model_freq", 10 ** 9))
+        self.save_model_start = int(cfg_get(cfg, "save_model_start", 0))
         self.log_dir = cfg_get(cfg, "log_dir", "") or "."
         self.checkpoint_dir = os.path.join(self.log_dir, "checkpoint")
 
@@ -109,6 +115,8 @@ class TrainAgent:
             raise AssertionError("lora: True must be used with load_pretrained_weights: True")
         model = PiZero(cfg, use_ddp=self.multi_gpu, device=self.device, dtype=self.dtype, init="default")
         self.model = model
+        self._averaging_enabled = bool(cfg_get(cfg, "use_ema", False) or cfg_get(cfg, "use_swa", False))
+        self._resume_average = None
         resume = cfg_get(cfg, "resume_checkpoint_path")
         if resume:
             self.load_checkpoint(resume)
@@ -119,6 +127,11 @@ class TrainAgent:
         if self.lora:  # train.py:101-102
             model.freeze_non_lora_weights_in_vlm()
         self.model_meta = PiZeroDDP(model) if self.multi_gpu else model
+        # every rank keeps its own average: the weights are identical across ranks, so nothing is communicated
+        self.model_averaging = ModelAveraging(model, cfg, self.device)
+        if self._resume_average is not None:
+            self.model_averaging.load_average(*self._resume_average)
+            self._resume_average = None
 
         per_dev = int(cfg_get(cfg, "per_device_batch_size"))
         self.grad_accumulation_steps = max(int(cfg_get(cfg, "global_batch_size")) // per_dev // self.world, 1)
@@ -151,6 +164,19 @@ class TrainAgent:
                                                        float(cfg_get(cfg, "flow_beta", 1)))
         if resume:
             self.load_optimizer(resume)
+
+        # in-training validation (train.py:132-160,413-459): on with a val_dataset or a ``data.val`` config node
+        self.run_eval = val_dataset is not None or cfg_get(cfg, "data.val") is not None
+        self.last_eval = None
+        if self.run_eval:
+            self.eval_freq = int(cfg_get(cfg, "eval_freq", 2000))
+            self.eval_thresholds = [float(x) for x in cfg_get(cfg, "eval_thresholds", [0.05, 0.1, 0.2, 0.3, 0.5])]
+            self.per_device_num_eval_batch = int(cfg_get(cfg, "eval_size", 1024)) // per_dev // self.world
+            if self.per_device_num_eval_batch < 1:
+                raise ValueError("eval_size is smaller than one batch per rank (per_device_batch_size x world size)")
+            self.val_dataloader = (val_dataset if val_dataset is not None
+                                   else SyntheticBridgeDataset(cfg, per_dev, seed=10_000 + self.rank))
+            self.val_dataiterator = None
 
     def sample_fm_time(self, bsz):
         """train.py:239-247."""
@@ -206,12 +232,17 @@ class TrainAgent:
                 for opt in self.optimizers:
                     opt.zero_grad(set_to_none=True)
                 self.cnt_update += 1
-                if self.cnt_update % self.save_model_freq == 0 or self.cnt_update == self.n_updates:
+                self.model_averaging.maybe_initialize(self.cnt_update)
+                self.model_averaging.maybe_update(self.cnt_update)
+                if ((self.cnt_update % self.save_model_freq == 0 and self.cnt_update > self.save_model_start)
+                        or self.cnt_update == self.n_updates):
                     self.save_training(self.cnt_update, self.cnt_batch)
             # every micro-batch's loss enters the window (kept on the device: no sync), as the reference's
             # deque of grad_accumulation_steps rank-mean losses (train.py:405-463); the window is all-reduced
             # ONCE, on the logged batches only (every rank has the same cnt_batch, so all enter the collective)
             loss_deque.append(loss.detach().reshape(1).float())
+            if self.run_eval and (self.cnt_batch + 1) % self.eval_freq == 0:
+                self.evaluate()
             if self.cnt_batch % self.log_freq == 0:
                 win = torch.cat(list(loss_deque))
                 if self.multi_gpu:
@@ -223,31 +254,82 @@ class TrainAgent:
             self.cnt_batch += 1
         return self
 
+    # ----------------------------------------------------------- validation --
+    def evaluate(self):
+        """train.py:413-459: ``per_device_num_eval_batch`` validation batches through ``infer_action`` on the averaged
+        weights (the live ones before averaging starts), action accuracy per threshold and L1 loss, averaged over
+        batches and ranks.  The live weights and train mode are restored.  Returns (and keeps as ``last_eval``)
+        {"l1": float, "accuracy": [float per threshold], "cnt_batch": int}."""
+        from src.utils.metric import get_action_accuracy
+
+        n = self.per_device_num_eval_batch
+        if self.main_rank:
+            log.info("Running evaluation for %d batches...", n)
+        if self.val_dataiterator is None:
+            self.val_dataiterator = iter(self.val_dataloader)
+        acc = torch.zeros(len(self.eval_thresholds), device=self.device)
+        l1 = torch.tensor(0.0, device=self.device)
+        self.model_meta.eval()
+        try:
+            with self.model_averaging.averaged_weights() as model_eval, torch.no_grad():
+                for _ in range(n):
+                    inputs = self.preprocess_batch(next(self.val_dataiterator), split_mask=True, sample_fm_time=False)
+                    gt_actions = inputs.pop("actions")
+                    preds = model_eval.infer_action(**inputs)
+                    acc += get_action_accuracy(gt_actions, preds, self.eval_thresholds)
+                    l1 += torch.nn.functional.l1_loss(preds, gt_actions)
+        finally:
+            self.model_meta.train()
+        acc /= n
+        l1 /= n
+        if self.multi_gpu:
+            torch.distributed.all_reduce(acc, op=torch.distributed.ReduceOp.SUM)
+            torch.distributed.all_reduce(l1, op=torch.distributed.ReduceOp.SUM)
+            acc /= self.world
+            l1 /= self.world
+        self.last_eval = {"l1": float(l1), "accuracy": [float(x) for x in acc], "cnt_batch": int(self.cnt_batch)}
+        if self.main_rank:
+            log.info("Eval | l1 Loss: %.3f | %s", self.last_eval["l1"],
+                     " | ".join(f"acc thres {t}: {a:.3f}" for t, a in zip(self.eval_thresholds,
+                                                                          self.last_eval["accuracy"])))
+        return self.last_eval
+
     # ---------------------------------------------------------- checkpoints --
     def save_training(self, cnt_update, cnt_batch):
         if not self.main_rank or not cfg_get(self.cfg, "log_dir"):
             return None
         os.makedirs(self.checkpoint_dir, exist_ok=True)
+        # train.py:500-512: once averaging is active "model" holds the AVERAGED weights (read from the average buffer:
+        # the same bits the model computes with inside averaged_weights()) and n_averaged their count
+        avg_state = self.model_averaging.state_dict()
+        weights = avg_state["state_dict"] if avg_state else self.model.state_dict()
         data = {
             "cnt_update": cnt_update, "cnt_batch": cnt_batch,
-            "model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+            "model": {k: v.detach().clone() for k, v in weights.items()},
             "action_optimizer": self.action_optimizer.state_dict(),
             "vlm_optimizer": self.vlm_optimizer.state_dict() if self.train_vlm else None,
             "action_lr_scheduler": self.action_lr_scheduler.state_dict(),
             "vlm_lr_scheduler": self.vlm_lr_scheduler.state_dict() if self.train_vlm else None,
-            "wandb_id": None, "n_averaged": 1,
+            "wandb_id": None, "n_averaged": avg_state.get("n_averaged", 1),
         }
+        if avg_state:  # extension: the live weights, so that a resumed run continues both exactly
+            data["model_train"] = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
         path = os.path.join(self.checkpoint_dir, f"step{cnt_update}.pt")
         torch.save(data, path)
         return path
 
     def load_checkpoint(self, path):
-        """train.py:531-544: counters + weights (strict, ``_orig_mod.`` prefix of compiled saves stripped)."""
+        """train.py:531-544: counters + weights (strict, ``_orig_mod.`` prefix of compiled saves stripped).
+        With averaging enabled and a checkpoint that holds "model_train": live <- "model_train", and "model" with
+        n_averaged is kept for the average (restored once ModelAveraging is built)."""
         data = torch.load(path, weights_only=True, map_location="cpu")
         self.cnt_update = int(data["cnt_update"])
         self.cnt_batch = int(data["cnt_batch"])
         self.wandb_id = data.get("wandb_id")
         sd = {k.replace("_orig_mod.", ""): v for k, v in data["model"].items()}
+        if self._averaging_enabled and data.get("model_train") is not None:
+            self._resume_average = (sd, int(data.get("n_averaged", 1)))
+            sd = data["model_train"]
         self.model.load_state_dict(sd, strict=True)
         log.info("Loaded model from %s at update %d batch %d", path, self.cnt_update, self.cnt_batch)
         return data
