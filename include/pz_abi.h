@@ -419,6 +419,29 @@ typedef struct pz_adamw8_args {
 } pz_adamw8_args;
 int pz_adamw8bit(const pz_adamw8_args* a, void* stream);
 
+/* Compensated and stochastic bf16 weight updates (csrc/pz_optim.hip).  Entry points added under ABI 22
+ * (no existing signature or struct changed).  pz_adamw8bit / pz_adamw round the fp32 result pv of an update to the
+ * nearest bf16, which returns the old weight whenever the step is below half an ulp of it.  These two compute the
+ * same pv and store it differently:
+ *   mode 1, compensated: comp (bf16, indexed like p, 8-byte aligned, disjoint from p) holds a second word c per
+ *     weight.  The update starts from w = p + c (fp32) in place of p; p' = bf16_rne(pv), c' = bf16_rne(pv - p'),
+ *     c' = 0 when pv is not finite.
+ *   mode 2, stochastic (comp ignored): p' = the top 16 bits of (bits(pv) + r); bf16_rne(pv) when pv's exponent
+ *     field is all ones.  r is 16 bits of a counter-based draw: with i = rng_base + (the element's index in the
+ *     run), r = (splitmix64(rng_key + (i >> 2)) >> (16 * (i & 3))) & 0xffff.  rng_base >= 0 is the arena index of
+ *     the run's element 0, so a draw depends on (rng_key, arena index) alone, not on how parameters fall into runs.
+ * Any other mode, a null / misaligned / overlapping comp in mode 1, rng_base < 0: PZ_ERR_INVALID_ARG before any
+ * launch.  Every operation rounded separately; deterministic, no atomics.
+ * pz_adamw8bit_r: pz_adamw8bit's update and state (same args struct).
+ * pz_adamw_r: fp32 moments, pz_adamw's expression in its order (p *= 1 - lr*wd; m, v; p -= (lr/bc1) * m /
+ *   (sqrt(v) / sqrt(bc2) + eps)) with every operation rounded on its own (pz_adamw's may contract to FMAs, so the
+ *   two differ in the last bit of pv); p / g 8-byte and m / v 16-byte aligned. */
+int pz_adamw8bit_r(const pz_adamw8_args* a, void* comp, int32_t mode, uint64_t rng_key, int64_t rng_base,
+                   void* stream);
+int pz_adamw_r(void* p, void* comp, const void* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+               float eps, float wd, float bc1, float bc2, const float* gscale, int32_t mode, uint64_t rng_key,
+               int64_t rng_base, void* stream);
+
 /* deterministic counter-based fill (oracle/synth.py twin): x[i] = off + scale*u(seed, i) */
 int pz_fill_uniform(void* x, int32_t out_fp32, int64_t n, uint64_t seed, float off, float scale,
                     void* stream);

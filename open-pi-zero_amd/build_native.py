@@ -21,13 +21,16 @@ OUT = os.path.join(HERE, "libpizero_hip.so")
 BUILD = os.path.join(HERE, "build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
-SOURCES = ["pz_gemm.hip", "pz_gemm_rows.hip", "pz_gemm_tall.hip", "pz_norm.hip", "pz_attn.hip", "pz_misc.hip", "pz_flash.hip", "pz_optim.hip", "pz_gemv.hip", "pz_decode.hip", "pz_quant.hip", "pz_adaln.hip", "pz_lora.hip", "pz_avg.hip"]
+SOURCES = ["pz_gemm.hip", "pz_gemm_rows.hip", "pz_gemm_tall.hip", "pz_norm.hip", "pz_attn.hip", "pz_misc.hip", "pz_flash.hip", "pz_optim.hip", "pz_optim_r.hip", "pz_gemv.hip", "pz_decode.hip", "pz_quant.hip", "pz_adaln.hip", "pz_lora.hip", "pz_avg.hip"]
 HEADERS = [os.path.join(CSRC, "pz_common.h"), os.path.join(CSRC, "pz_gemm_epi.h"), os.path.join(ROOT, "include", "pz_abi.h")]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result",
          "-Wno-unused-value", "-munsafe-fp-atomics"]
 # per-file extra flags: the 8-bit optimizer is held bit-exact to its float32 oracle, so no FMA contraction; the
 # weight-averaging lerp is held bit-exact to torch.lerp (its two FMAs are explicit)
-FILE_FLAGS = {"pz_optim.hip": ["-ffp-contract=off"], "pz_avg.hip": ["-ffp-contract=off"]}
+FILE_FLAGS = {"pz_optim.hip": ["-ffp-contract=off"], "pz_optim_r.hip": ["-ffp-contract=off"],
+              "pz_avg.hip": ["-ffp-contract=off"]}
+# sources that include another source: pz_optim_r.hip is pz_optim.hip's second object (the rounding entry points)
+FILE_DEPS = {"pz_optim_r.hip": ["pz_optim.hip"]}
 
 
 def _needs(obj: str, deps: list[str]) -> bool:
@@ -40,7 +43,7 @@ def _needs(obj: str, deps: list[str]) -> bool:
 def _compile(src: str, force: bool) -> str:
     s = os.path.join(CSRC, src)
     obj = os.path.join(BUILD, src.replace(".hip", ".o"))
-    if force or _needs(obj, [s] + HEADERS):
+    if force or _needs(obj, [s] + [os.path.join(CSRC, d) for d in FILE_DEPS.get(src, [])] + HEADERS):
         cmd = [HIPCC, *FLAGS, *FILE_FLAGS.get(src, []), "-c", s, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:

@@ -471,13 +471,6 @@ __global__ void clip_coef_kernel(const float* __restrict__ parts, int64_t nparts
   }
 }
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 __global__ void fill_uniform_kernel(void* x, int out_fp32, int64_t n, uint64_t seed, float off, float scale) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const uint64_t z = splitmix64(seed + (uint64_t)i);

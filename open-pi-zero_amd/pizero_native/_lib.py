@@ -175,6 +175,8 @@ SIGNATURES = {
     "pz_act_bwd": [vp, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp],
     "pz_adamw": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, vp, vp],
     "pz_adamw8bit": [C.POINTER(AdamW8Args), vp],
+    "pz_adamw8bit_r": [C.POINTER(AdamW8Args), vp, i32, C.c_uint64, i64, vp],
+    "pz_adamw_r": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, vp, i32, C.c_uint64, i64, vp],
     "pz_sumsq": [vp, i64, vp, vp],
     "pz_clip_coef": [vp, i64, vp, vp, f32, vp],
     "pz_fill_uniform": [vp, i32, i64, C.c_uint64, f32, f32, vp],

@@ -730,9 +730,28 @@ def adamw(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2, gscale=None):
          float(wd), float(bc1), float(bc2), _p(gscale), _st())
 
 
-def adamw8bit(run, g, qmap1, qmap2, lr, b1, b2, eps, wd, t, gscale=None):
-    """One bnb-style 8-bit AdamW step over a contiguous run (optim.FusedAdamW._prepare_8bit layout).
-    Host precomputes the float32 constants exactly as oracle/adamw8bit.py does."""
+ROUND_COMPENSATED, ROUND_STOCHASTIC = 1, 2  # pz_adamw8bit_r / pz_adamw_r modes (include/pz_abi.h)
+
+
+def splitmix64(z):
+    """The kernels' counter-based hash (csrc/pz_common.h) on the host: the stochastic-rounding key of a step."""
+    m = 2 ** 64 - 1
+    z = (z + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
+def adamw_r(p, comp, g, m, v, lr, b1, b2, eps, wd, bc1, bc2, gscale=None, *, mode, rng_key=0, rng_base=0):
+    """``adamw`` with a compensated (mode 1: ``comp`` is the bf16 compensation buffer, laid out like ``p``) or
+    stochastic (mode 2: draws from ``rng_key`` and the arena index ``rng_base`` of p[0]) weight store."""
+    call("pz_adamw_r", _p(p), _p(comp), _p(g), _p(m), _p(v), p.numel(), float(lr), float(b1), float(b2), float(eps),
+         float(wd), float(bc1), float(bc2), _p(gscale), int(mode), C.c_uint64(int(rng_key) & (2 ** 64 - 1)),
+         int(rng_base), _st())
+
+
+def _adamw8_args(run, g, qmap1, qmap2, lr, b1, b2, eps, wd, t, gscale):
+    """pz_adamw8_args of one run.  Host precomputes the float32 constants exactly as oracle/adamw8bit.py does."""
     import numpy as np
 
     f = np.float32
@@ -751,7 +770,22 @@ def adamw8bit(run, g, qmap1, qmap2, lr, b1, b2, eps, wd, t, gscale=None):
     a.epsc = float(f(f(eps) * c2))
     a.decay = float(f(1.0 - lr * wd)) if wd > 0 else 1.0
     a.gscale = _p(gscale)
+    return a
+
+
+def adamw8bit(run, g, qmap1, qmap2, lr, b1, b2, eps, wd, t, gscale=None):
+    """One bnb-style 8-bit AdamW step over a contiguous run (optim.FusedAdamW._prepare_8bit layout)."""
+    a = _adamw8_args(run, g, qmap1, qmap2, lr, b1, b2, eps, wd, t, gscale)
     call("pz_adamw8bit", C.byref(a), _st())
+
+
+def adamw8bit_r(run, g, qmap1, qmap2, lr, b1, b2, eps, wd, t, gscale=None, *, comp=None, mode, rng_key=0,
+                rng_base=0):
+    """``adamw8bit`` with a compensated (mode 1, ``comp``) or stochastic (mode 2, ``rng_key`` / ``rng_base``) weight
+    store: same update, same state."""
+    a = _adamw8_args(run, g, qmap1, qmap2, lr, b1, b2, eps, wd, t, gscale)
+    call("pz_adamw8bit_r", C.byref(a), _p(comp), int(mode), C.c_uint64(int(rng_key) & (2 ** 64 - 1)), int(rng_base),
+         _st())
 
 
 def sumsq(g, parts):

@@ -25,6 +25,21 @@ for 8-bit state; ``load_state_dict`` accepts either layout in either mode (8-bit
 dequantised, fp32 moments quantised).  State tensors are views of the flat buffers (torch.save
 stores each buffer once).  The global gradient norm is reduced without atomics (fixed
 partial-sum order), so clipping -- and training -- is bitwise reproducible.
+
+``rounding``.  The weights are bf16 only, and with ``"nearest"`` (the default: exactly the kernels
+and the state of before) a step smaller than half an ulp of a weight is rounded away in full -- at lr 5e-5 that is
+every weight with |p| >= 2^-6.  ``"compensated"`` keeps a second bf16 word per weight (one flat buffer per run,
++2 B per trained element) that carries what the rounding dropped into the next step; ``"stochastic"`` needs no
+state and rounds up or down with the probability that makes the stored weight unbiased.  Its draws are a pure
+function of (``seed``, the group's step, the element's index in the arena storage), so they do not depend on how
+parameters fall into runs or optimizers and are identical on every data-parallel rank.  In compensated mode every
+parameter's state gains ``"comp"`` (a bf16 view shaped like the parameter); ``rounding`` and ``seed`` are in the
+param_groups of the two new modes.  ``load_state_dict`` keeps the optimizer's own ``rounding``: a state without
+``"comp"`` starts it from zeros, a ``"comp"`` loaded into another mode is dropped; ``seed`` is taken from the
+loaded state (as the other hyperparameters are) when both sides have one.  Writes to the weights from outside
+the optimizer -- ``model.load_state_dict`` after construction, ``FlatAverage.swapped()`` -- leave the
+compensation word describing the weight it was computed for: stale by less than half an ulp of that weight,
+which is harmless (it is the size of one rounding), not an error that grows.
 """
 
 from __future__ import annotations
@@ -40,6 +55,7 @@ from ._lib import PZ_SUMSQ_PARTS
 _CHECK_FINITE = os.environ.get("PZ_CHECK_FINITE", "0") == "1"  # debug: check the updated weights (engine._chk)
 BLOCK8 = 256  # elements per absmax block (bnb blockwise 2-state optimizers)
 MIN_8BIT_SIZE = 4096  # bnb Optimizer8bit min_8bit_size: smaller tensors keep fp32 state
+ROUNDINGS = ("nearest", "compensated", "stochastic")  # FusedAdamW(rounding=...): how pv becomes the bf16 weight
 
 
 def create_dynamic_map(signed=True, max_exponent_bits=7, total_bits=8):
@@ -94,11 +110,19 @@ def contiguous_runs(params):
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, state_bits=32):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, state_bits=32,
+                 rounding="nearest", seed=0):
         if state_bits not in (32, 8):
             raise ValueError("state_bits must be 32 or 8")
+        if rounding not in ROUNDINGS:
+            raise ValueError(f"rounding must be one of {', '.join(ROUNDINGS)}, got {rounding!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.state_bits = state_bits
+        self.rounding = rounding
+        self.seed = int(seed)
+        if rounding != "nearest":  # the nearest-mode param_groups (and state dict) keep exactly their keys
+            for group in self.param_groups:
+                group["rounding"], group["seed"] = rounding, int(seed)
         self._runs = None
         self._gscale = None
         self._parts = None
@@ -112,7 +136,9 @@ class FusedAdamW(torch.optim.Optimizer):
             runs = []
             for flat, plist, off in contiguous_runs(group["params"]):
                 dev = flat.device
-                r = dict(flat=flat, params=plist)
+                r = dict(flat=flat, params=plist, off=off)  # off: the run's element offset in the arena storage
+                if self.rounding == "compensated":
+                    r["comp"] = torch.zeros(flat.numel(), device=dev, dtype=flat.dtype)
                 if self.state_bits == 32:
                     r["m"] = torch.zeros(flat.numel(), device=dev, dtype=torch.float32)
                     r["v"] = torch.zeros_like(r["m"])
@@ -158,6 +184,8 @@ class FusedAdamW(torch.optim.Optimizer):
         """Device bytes of optimizer state (reported by bench.py)."""
         self._prepare()
         keys = ("m", "v") if self.state_bits == 32 else ("s1", "s2", "absmax1", "absmax2", "m32", "v32")
+        if self.rounding == "compensated":
+            keys += ("comp",)
         return sum(r[k].numel() * r[k].element_size() for runs in self._runs for r in runs for k in keys)
 
     def _moment_views(self):
@@ -186,6 +214,18 @@ class FusedAdamW(torch.optim.Optimizer):
                     else:
                         out[p] = {"state1": r["m32"][b:b + p.numel()].view(p.shape),
                                   "state2": r["v32"][b:b + p.numel()].view(p.shape)}
+        return out
+
+    def _comp_views(self):
+        """param -> its compensation words, a bf16 view shaped like the parameter (compensated mode)."""
+        self._prepare()
+        out = {}
+        for runs in self._runs:
+            for r in runs:
+                base, es = r["flat"].data_ptr(), r["flat"].element_size()
+                for p in r["params"]:
+                    o = (p.data_ptr() - base) // es
+                    out[p] = r["comp"][o:o + p.numel()].view(p.shape)
         return out
 
     def _n_runs(self):
@@ -233,7 +273,9 @@ class FusedAdamW(torch.optim.Optimizer):
                 g = self._flat_grad(r)
                 if g is None:
                     continue
-                if self.state_bits == 32:
+                if self.rounding != "nearest":
+                    self._step_rounded(group, r, g, t)
+                elif self.state_bits == 32:
                     ops.adamw(r["flat"], g, r["m"], r["v"], group["lr"], b1, b2, group["eps"],
                               group["weight_decay"], 1 - b1 ** t, 1 - b2 ** t, self._gscale)
                 else:
@@ -248,6 +290,20 @@ class FusedAdamW(torch.optim.Optimizer):
                     check_finite(f"FusedAdamW.step (group lr {group['lr']:g})", param=r["flat"])
         self._gscale = None
 
+    def _step_rounded(self, group, r, g, t):
+        """One run's step with the compensated / stochastic weight store (pz_adamw_r / pz_adamw8bit_r)."""
+        b1, b2 = group["betas"]
+        kw = dict(mode=ops.ROUND_COMPENSATED, rng_key=0, rng_base=r["off"])
+        if self.rounding == "stochastic":
+            kw.update(mode=ops.ROUND_STOCHASTIC,
+                      rng_key=ops.splitmix64((int(group.get("seed", self.seed)) + t) & (2 ** 64 - 1)))
+        if self.state_bits == 32:
+            ops.adamw_r(r["flat"], r.get("comp"), g, r["m"], r["v"], group["lr"], b1, b2, group["eps"],
+                        group["weight_decay"], 1 - b1 ** t, 1 - b2 ** t, self._gscale, **kw)
+        else:
+            ops.adamw8bit_r(r, g, self._qmap1, self._qmap2, group["lr"], b1, b2, group["eps"],
+                            group["weight_decay"], t, self._gscale, comp=r.get("comp"), **kw)
+
     def zero_grad(self, set_to_none: bool = True):
         for group in self.param_groups:
             for p in group["params"]:
@@ -260,9 +316,11 @@ class FusedAdamW(torch.optim.Optimizer):
     def state_dict(self):
         """32-bit: torch.optim.AdamW layout {i: {step, exp_avg, exp_avg_sq}}; 8-bit: bnb's layout
         {i: {step, state1, state2, absmax1, absmax2, qmap1, qmap2}} (fp32 state1/state2 for small
-        tensors); param_groups with integer ids."""
+        tensors); param_groups with integer ids.  Compensated rounding: every parameter's state also has "comp";
+        compensated / stochastic: the param_groups also have "rounding" and "seed"."""
         self._prepare()
         views = self._moment_views() if self.state_bits == 32 else self._state8_views()
+        comp = self._comp_views() if self.rounding == "compensated" else None
         state, groups, i = {}, [], 0
         for group in self.param_groups:
             ids = []
@@ -278,6 +336,8 @@ class FusedAdamW(torch.optim.Optimizer):
                         if "absmax1" in st:
                             st["qmap1"], st["qmap2"] = self._qmap1, self._qmap2
                         state[i] = st
+                    if comp is not None:
+                        state[i]["comp"] = comp[p]
                 ids.append(i)
                 i += 1
             g = {k: v for k, v in group.items() if k != "params"}
@@ -311,12 +371,14 @@ class FusedAdamW(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         """Accepts the torch.optim.AdamW layout or bnb's AdamW8bit layout, in either state mode:
         moments are copied (fp32 <- fp32, codes <- codes) or converted (dequantised / quantised
-        with a per-block absmax)."""
+        with a per-block absmax).  The rounding mode stays this optimizer's: "comp" is copied in compensated mode
+        (zeros where the state has none) and ignored in the others."""
         saved = state_dict["param_groups"]
         if len(saved) != len(self.param_groups):
             raise ValueError("loaded state dict has a different number of parameter groups")
         self._prepare()
         views = self._moment_views() if self.state_bits == 32 else self._state8_views()
+        comp = self._comp_views() if self.rounding == "compensated" else None
         st = state_dict["state"]
         for group, sg in zip(self.param_groups, saved):
             if len(sg["params"]) != len(group["params"]):
@@ -326,6 +388,11 @@ class FusedAdamW(torch.optim.Optimizer):
             for pid, p in zip(sg["params"], group["params"]):
                 s = st.get(pid)
                 dst = views[p]
+                if comp is not None:
+                    if s is not None and "comp" in s:
+                        comp[p].copy_(s["comp"].to(comp[p].device, comp[p].dtype).reshape(comp[p].shape))
+                    else:
+                        comp[p].zero_()
                 if s is None:
                     for x in (dst if isinstance(dst, tuple) else dst.values()):
                         x.zero_()
@@ -357,8 +424,9 @@ class FusedAdamW(torch.optim.Optimizer):
                         nrm = torch.where(am[blk] > 0, xf / am[blk].clamp_min(1e-38), torch.zeros_like(xf))
                         dst["state" + k].copy_(_quantize_nearest(nrm, q).view(p.shape))
             for k, val in sg.items():
-                if k != "params":
-                    group[k] = val
+                if k == "params" or k == "rounding" or (k == "seed" and self.rounding == "nearest"):
+                    continue  # the rounding mode is this optimizer's own
+                group[k] = val
             group["step"] = int(step or 0)
 
 

@@ -17,6 +17,9 @@ MI355X-native pieces: pizero_native.ddp.PiZeroDDP (RCCL bucketed all-reduce
 overlapped with backward), pizero_native.optim.FusedAdamW (flat fused AdamW; by default
 with the reference's blockwise 8-bit state, ``optimizer_state_bits: 8`` -- the algorithm of
 bitsandbytes' AdamW8bit restated, bitsandbytes itself absent: parity with it unpinned).
+An extension: ``optimizer_rounding: compensated | stochastic`` (default ``nearest``, the reference's behaviour)
+keeps steps smaller than half a bf16 ulp of a weight instead of rounding them away; its state travels in the
+optimizer state dicts, so a resumed run continues bit for bit.
 Data: the OXE/RLDS TensorFlow pipeline is out of scope; the
 agent consumes any iterable of reference-format batches, by default
 ``SyntheticBridgeDataset`` (bridge-shaped random batches, already tokenized).
@@ -140,9 +143,12 @@ class TrainAgent:
         self.train_vlm = bool(cfg_get(cfg, "train_vlm", True))
         # the reference's bnb AdamW8bit (train.py:171-175): blockwise 8-bit state by default
         self.state_bits = int(cfg_get(cfg, "optimizer_state_bits", 8))
+        # how the fp32 update becomes the bf16 weight (FusedAdamW): nearest | compensated | stochastic
+        rounding = dict(rounding=cfg_get(cfg, "optimizer_rounding", "nearest"),
+                        seed=int(cfg_get(cfg, "optimizer_rounding_seed", cfg_get(cfg, "seed", 0))))
         self.action_optimizer = FusedAdamW(model.action_expert_parameters, lr=cfg_get(cfg, "action_lr"),
                                            weight_decay=cfg_get(cfg, "action_weight_decay", 0.0),
-                                           state_bits=self.state_bits)
+                                           state_bits=self.state_bits, **rounding)
         sch = lambda opt, key, lr: CosineAnnealingWarmupRestarts(  # noqa: E731
             opt, first_cycle_steps=cfg_get(cfg, f"{key}.first_cycle_steps"), cycle_mult=1.0, max_lr=lr,
             min_lr=cfg_get(cfg, f"{key}.min_lr"), warmup_steps=cfg_get(cfg, f"{key}.warmup_steps"), gamma=1.0)
@@ -152,7 +158,7 @@ class TrainAgent:
             vlm_params = model.lora_trainable_vlm_parameters if self.lora else model.trainable_vlm_parameters
             self.vlm_optimizer = FusedAdamW(vlm_params, lr=cfg_get(cfg, "vlm_lr"),
                                             weight_decay=cfg_get(cfg, "vlm_weight_decay", 0.0),
-                                            state_bits=self.state_bits)
+                                            state_bits=self.state_bits, **rounding)
             self.vlm_lr_scheduler = sch(self.vlm_optimizer, "vlm_lr_scheduler", cfg_get(cfg, "vlm_lr"))
             self.optimizers.append(self.vlm_optimizer)
         else:
