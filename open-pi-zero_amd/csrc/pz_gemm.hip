@@ -301,25 +301,8 @@ __global__ void __launch_bounds__(256) splitk_epilogue_kernel(GemmP p, int S) {
   });
 }
 
-// -------------------------------------------------------------------------
-// 256x256 tile, 512 threads = 8 waves (4 along M x 2 along N, 64x128 per wave),
-// operands streamed global -> LDS by LDS-DMA (global_load_lds_dwordx4, 1 KiB per
-// wave-instruction, no VGPR staging).  Two pipelines are built from one body:
-//   BK2 = 64, 2 stages (2 x 64 KiB): the next K-tile's DMA is issued before the
-//     current tile's 64 MFMAs per wave; one vmcnt(0) + barrier per K step;
-//   BK2 = 32, 4-slot ring (4 x 32 KiB): three K-tiles in flight, counted
-//     vmcnt (never 0 in steady state) + raw s_barrier per K step.
-// Measured on MI355X (tools/gemm_bench.py, random bf16): the 64/2-stage form
-// is faster on every Pi0 shape (fewer barriers outweigh the deeper prefetch),
-// so it is the one dispatched; the ring is kept for A/B experiments.
-// LDS images are XOR-swizzled for conflict-free ds_read_b128 (k-contiguous
-// operands) and ds_read_b64_tr_b16 (k-strided operands, [k][row] 512-B rows);
-// the swizzle is applied to each lane's GLOBAL source address because an
-// LDS-DMA write is lane-linear.  Requires K % BK2 == 0; M/N tails clamp the
-// source rows (clamped rows are never stored).  GEGLU: B rows interleave
-// gate/up in 64-row blocks so each wave's 128 virtual columns are 64 gate +
-// the matching 64 up columns.
-// -------------------------------------------------------------------------
+// 256 x 256 tiles, 512 threads = 8 waves; operands streamed global -> LDS by LDS-DMA (global_load_lds_dwordx4,
+// 1 KiB per wave-instruction, no VGPR staging)
 constexpr int BT = 256, NT2 = 512;
 
 __device__ __forceinline__ void glds16(const bf16_t* src, char* lds_base) {
@@ -327,187 +310,19 @@ __device__ __forceinline__ void glds16(const bf16_t* src, char* lds_base) {
                                    (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
 }
 
-// k-contiguous image [256 rows][BKT k]: 16-B chunk ch of row r lives at chunk ch ^ swz(r)
-template <int BKT>
-__device__ __forceinline__ int swz_kc(int r) {
-  return BKT == 64 ? ((r >> 1) & 7) : 3 * ((r >> 3) & 1);
-}
-
-// global source of lane `lane` for DMA instruction j of an operand tile (BKT*256*2/1024 instructions)
-template <bool KC, int BKT>
-__device__ __forceinline__ const bf16_t* dma_src(const bf16_t* base, int64_t ld, int j, int lane, int64_t row0,
-                                                 int64_t R, bool geglu, int64_t gI) {
-  if (KC) {
-    constexpr int CPR = BKT / 8;          // 16-B chunks per row
-    constexpr int RPI = 64 / CPR;         // rows per 1 KiB instruction
-    const int r = RPI * j + lane / CPR;
-    const int kc = (lane % CPR) ^ swz_kc<BKT>(r);
-    int64_t grow;
-    if (geglu) {
-      const int blk = r >> 6;
-      int64_t idx = row0 + (blk >> 1) * 64 + (r & 63);
-      idx = idx < gI ? idx : gI - 1;
-      grow = (blk & 1) ? gI + idx : idx;
-    } else {
-      grow = row0 + r;
-      grow = grow < R ? grow : R - 1;
-    }
-    return base + grow * ld + 8 * kc;
-  } else {
-    const int k = 2 * j + (lane >> 5);
-    const int c = (2 * (lane & 31)) ^ sw_tr(k);
-    int64_t r = row0 + 4 * c;
-    r = r <= R - 8 ? r : R - 8;
-    return base + (int64_t)k * ld + r;
-  }
-}
-
-template <bool KC, int BKT>
-__device__ __forceinline__ bf16x8 frag256(const char* lds, int rb, int kk, int lane) {
-  if (KC) {
-    const int r = rb * 16 + (lane & 15);
-    const int ch = kk * 4 + (lane >> 4);
-    return *reinterpret_cast<const bf16x8*>(lds + r * (BKT * 2) + ((ch ^ swz_kc<BKT>(r)) << 4));
-  } else {
-    return frag<false, 512>(lds, rb, kk, lane);
-  }
-}
-
 #define PZ_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define PZ_BARRIER()                                   \
-  do {                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __builtin_amdgcn_s_barrier();                      \
-    asm volatile("" ::: "memory");                     \
-  } while (0)
-
-template <bool AKC, bool BKC, bool GEGLU, int BKT>
-__global__ void __launch_bounds__(NT2, 1) gemm256_kernel(GemmP p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int MI = 4, NI = 8;
-  constexpr int NSTAGE = BKT == 64 ? 2 : 4;
-  constexpr int IMG = 256 * BKT * 2;
-  constexpr int STAGE = 2 * IMG;
-  constexpr int NI_DMA = IMG / 1024 / 8;  // DMA instructions per wave per operand per K-tile
-  int tm, tn;
-  tile_coords(blockIdx.x, gridDim.x, p.tiles_m, p.tiles_n, tm, tn);
-  const int64_t m0 = (int64_t)tm * BT;
-  const int64_t n0 = GEGLU ? (int64_t)tn * (BT / 2) : (int64_t)tn * BT;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int64_t z = blockIdx.y;
-  const int64_t zo = z / p.batch_inner, zi = z % p.batch_inner;
-  const bf16_t* Ab = p.A + zo * p.sAo + zi * p.sAi;
-  const bf16_t* Bb = p.B + zo * p.sBo + zi * p.sBi;
-  const int64_t cofs = zo * p.sCo + zi * p.sCi;
-  const int64_t rofs = zo * p.sRo + zi * p.sRi;
-
-  const bf16_t* sa[NI_DMA];
-  const bf16_t* sb[NI_DMA];
-#pragma unroll
-  for (int i = 0; i < NI_DMA; ++i) {
-    sa[i] = dma_src<AKC, BKT>(Ab, p.lda, wave * NI_DMA + i, lane, m0, p.M, false, 0);
-    sb[i] = dma_src<BKC, BKT>(Bb, p.ldb, wave * NI_DMA + i, lane, n0, p.N, GEGLU, p.geglu_I);
-  }
-  const int64_t stepA = AKC ? BKT : BKT * p.lda;
-  const int64_t stepB = BKC ? BKT : BKT * p.ldb;
-
-  f32x4 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = (int)(p.K / BKT);
-  auto issue = [&](int kt) {
-    char* ia = smem + (kt % NSTAGE) * STAGE;
-    char* ib = ia + IMG;
-#pragma unroll
-    for (int i = 0; i < NI_DMA; ++i) {
-      glds16(sa[i] + kt * stepA, ia + (wave * NI_DMA + i) * 1024);
-      glds16(sb[i] + kt * stepB, ib + (wave * NI_DMA + i) * 1024);
-    }
-  };
-  auto compute = [&](int kt) {
-    const char* a_img = smem + (kt % NSTAGE) * STAGE;
-    const char* b_img = a_img + IMG;
-#pragma unroll
-    for (int kk = 0; kk < BKT / 32; ++kk) {
-      bf16x8 bfr[NI];
-#pragma unroll
-      for (int j = 0; j < NI; ++j) bfr[j] = frag256<BKC, BKT>(b_img, wn * NI + j, kk, lane);
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const bf16x8 af = frag256<AKC, BKT>(a_img, wm * MI + i, kk, lane);
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af, acc[i][j], 0, 0, 0);
-      }
-    }
-  };
-  if constexpr (BKT == 64) {
-    issue(0);
-    PZ_WAIT_VM(0);
-    PZ_BARRIER();
-    for (int kt = 0; kt < nk; ++kt) {
-      if (kt + 1 < nk) issue(kt + 1);
-      compute(kt);
-      PZ_WAIT_VM(0);
-      PZ_BARRIER();
-    }
-  } else {
-    issue(0);
-    if (nk > 1) issue(1);
-    if (nk > 2) issue(2);
-    if (nk > 2) PZ_WAIT_VM(8);
-    else if (nk > 1) PZ_WAIT_VM(4);
-    else PZ_WAIT_VM(0);
-    PZ_BARRIER();
-    for (int kt = 0; kt < nk; ++kt) {
-      if (kt + 3 < nk) issue(kt + 3);
-      compute(kt);
-      if (kt + 3 < nk) PZ_WAIT_VM(8);  // retire tile kt+1, keep kt+2, kt+3 in flight
-      else if (kt + 2 < nk) PZ_WAIT_VM(4);
-      else PZ_WAIT_VM(0);
-      PZ_BARRIER();
-    }
-  }
-  if (GEGLU) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      const int64_t m = m0 + wm * 64 + i * 16 + (lane & 15);
-#pragma unroll
-      for (int j = 0; j < NI / 2; ++j)
-        store_geglu4(p, cofs, m, n0 + wn * 64 + j * 16 + 4 * (lane >> 4), acc[i][j], acc[i][j + NI / 2]);
-    }
-  } else {
-    epi_dispatch(p, [&](auto em) {
-      constexpr int EM = decltype(em)::value;
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int64_t m = m0 + wm * 64 + i * 16 + (lane & 15);
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-          store_out4_m<EM>(p, cofs, rofs, m, n0 + wn * 128 + j * 16 + 4 * (lane >> 4), acc[i][j]);
-      }
-    });
-  }
-}
-
-constexpr int BK256 = 64;  // dispatched K-tile of the 256 kernel (see above)
 
 // -------------------------------------------------------------------------
 // 256x256x64 "8-phase" ping-pong GEMM (the dispatched large-GEMM kernel).
 //
 // 8 waves as 2 (M) x 4 (N), 128 x 64 outputs per wave (acc[8][4], 128 AGPR/VGPR).
-// With A k-contiguous (every forward GEMM and the large NN dgrads) each 64-deep K-tile
-// is consumed in 2 sections of 32 MFMAs: section 0 reads A-lo + all of B and runs
-// output quadrants (0,0) (0,1), section 1 reads A-hi and runs (1,1) (1,0).  Every
-// section = [issue LDS-DMA pieces, ds_reads, counted vmcnt, lgkmcnt(0)] barrier
-// [32 MFMA at setprio 1] barrier.  (A k-strided, PZ_GEMM_MAIN=quad only: the older
-// 4 phases of 16 MFMAs, order (0,0) (0,1) (1,1) (1,0), reads A-lo + B-lo / B-hi /
-// A-hi / nothing.)  The M-row-1 wave group runs one barrier behind the row-0 group,
+// A is k-contiguous (every forward GEMM and the large NN dgrads; a k-strided A takes
+// gemm8k_kernel).  Each 64-deep K-tile is consumed in 2 sections of 32 MFMAs: section 0
+// reads A-lo + all of B and runs output quadrants (0,0) (0,1), section 1 reads A-hi and
+// runs (1,1) (1,0).  Every section = [issue LDS-DMA pieces, ds_reads, counted vmcnt,
+// lgkmcnt(0)] barrier [32 MFMA at setprio 1] barrier.  (The older schedule of 4 phases
+// of 16 MFMAs measured slower: profiles/r05/feed_ab_*.log.)
+// The M-row-1 wave group runs one barrier behind the row-0 group,
 // so on every SIMD (waves w and w+4) one wave's MFMAs overlap the other's LDS reads
 // / DMA issue.
 //
@@ -757,17 +572,14 @@ __device__ __forceinline__ void img_put(char* img, int row, int col, u32x2 v) {
   const int ch = col >> 3;
   *reinterpret_cast<u32x2*>(img + row * 256 + ((ch ^ (row & 15)) << 4) + ((col >> 2) & 1) * 8) = v;
 }
-// 16-B output store; nt: non-temporal (streaming) cache policy (PZ_GEMM_NT=1, A/B)
-__device__ __forceinline__ void st16(bf16_t* dst, const u32x4& v, bool nt) {
-  if (nt) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst));
-  else *reinterpret_cast<u32x4*>(dst) = v;
-}
-__device__ __forceinline__ void img_flush(const char* img, bf16_t* dst, int64_t ld, bool nt = false) {
+// 16-B output store (non-temporal stores measured no faster for C or the saved activations: profiles/r03/bench_ntaux.json)
+__device__ __forceinline__ void st16(bf16_t* dst, const u32x4& v) { *reinterpret_cast<u32x4*>(dst) = v; }
+__device__ __forceinline__ void img_flush(const char* img, bf16_t* dst, int64_t ld) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int c = threadIdx.x + i * NT2, row = c >> 4, ch = c & 15;
     const u32x4 v = *reinterpret_cast<const u32x4*>(img + row * 256 + ((ch ^ (row & 15)) << 4));
-    st16(dst + row * ld + ch * 8, v, nt);
+    st16(dst + row * ld + ch * 8, v);
   }
 }
 __device__ __forceinline__ void lds_sync() {
@@ -867,21 +679,21 @@ __device__ __forceinline__ void epi8p_staged(const GemmP& p, int64_t cofs, int64
           dg[e] = v[e] * x1[e] * gr_;
           du[e] = v[e] * gl_;
         }
-        st16(Cp, pack8v(dg), p.nt_store);
-        st16(Cp + p.geglu_I, pack8v(du), p.nt_store);
+        st16(Cp, pack8v(dg));
+        st16(Cp + p.geglu_I, pack8v(du));
       } else if (FM == FM_DACT) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] *= gelu ? gelu_tanh_grad(x0[e]) : silu_grad(x0[e]);
-        st16(Cp, pack8v(v), p.nt_store);
+        st16(Cp, pack8v(v));
       } else {
         if (act) {
-          if (p.aux) st16(p.aux + (m0 + row) * p.ld_aux + n0 + col, iv[i], p.nt_aux);
+          if (p.aux) st16(p.aux + (m0 + row) * p.ld_aux + n0 + col, iv[i]);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = gelu ? gelu_tanh(v[e]) : silu(v[e]);
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += x1[e] + x0[e];  // resid, old C (zeros when absent)
-        st16(Cp, pack8v(v), p.nt_store);
+        st16(Cp, pack8v(v));
       }
     }
   }
@@ -969,13 +781,12 @@ __device__ __forceinline__ void epilogue8p(const GemmP& p, int64_t cofs, int64_t
           const int row = wr * 128 + rb * 16 + rl, col = wc * 32 + j * 16 + g4;
           img_put(smem, row, col, u32x2{pack2bf(hh[0], hh[1]), pack2bf(hh[2], hh[3])});
           img_put(smem + 65536, row, col, u32x2{pack2bf(gg[0], gg[1]), pack2bf(gg[2], gg[3])});
-          if (p.nt_aux) __builtin_nontemporal_store(pk4(uu), reinterpret_cast<u32x2*>(Ur + j * 16));
-          else *reinterpret_cast<u32x2*>(Ur + j * 16) = pk4(uu);
+          *reinterpret_cast<u32x2*>(Ur + j * 16) = pk4(uu);
         }
       }
       lds_sync();
-      img_flush(smem, reinterpret_cast<bf16_t*>(p.C) + cofs + m0 * p.ldc + n0, p.ldc, p.nt_store);
-      img_flush(smem + 65536, p.aux + m0 * p.ld_aux + n0, p.ld_aux, p.nt_aux);
+      img_flush(smem, reinterpret_cast<bf16_t*>(p.C) + cofs + m0 * p.ldc + n0, p.ldc);
+      img_flush(smem + 65536, p.aux + m0 * p.ld_aux + n0, p.ld_aux);
       return;
     }
 #pragma unroll
@@ -1012,8 +823,8 @@ __device__ __forceinline__ void epilogue8p(const GemmP& p, int64_t cofs, int64_t
           }
         lds_sync();
         bf16_t* C = reinterpret_cast<bf16_t*>(p.C) + cofs + m0 * p.ldc + n0;
-        img_flush(smem, C, p.ldc, p.nt_store);
-        img_flush(smem + 65536, C + 128, p.ldc, p.nt_store);
+        img_flush(smem, C, p.ldc);
+        img_flush(smem + 65536, C + 128, p.ldc);
         break;
       }
       case FM_F32: epi8p_fast<FM_F32>(p, cofs, rofs, m, nb, acc); break;
@@ -1050,6 +861,7 @@ __device__ __forceinline__ void epilogue8p(const GemmP& p, int64_t cofs, int64_t
 template <bool AKC, bool BKC, bool GEGLU, bool KTAIL, bool F8, bool EXT = false>
 __device__ __forceinline__ void gemm8p_body(const GemmP& p) {
   static_assert(!EXT || (KTAIL && !F8), "rank extension: bf16, tail-capable instantiation");
+  static_assert(AKC, "a k-strided A takes gemm8k_kernel (use_khalf)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nk1 = (int)((p.K + 63) / 64);  // main K-tiles
   const int nk_all = EXT ? nk1 + (int)((p.K2 + 63) / 64) : nk1;
@@ -1216,156 +1028,60 @@ __device__ __forceinline__ void gemm8p_body(const GemmP& p) {
     __builtin_amdgcn_s_setprio(0);
   };
 
-  // Per-operand schedule.  k-contiguous operands stream region by region as soon as each is
-  // free (A: A1(kt+1) in phase 0, A0(kt+2) in phase 1; B: B0 in 2, B1 in 3); k-strided ones
-  // load both regions together (B in phase 2, A in phase 3) so every k-row's 512-B span is
-  // fetched by back-to-back instructions.  vmcnt counts (pieces of 2 DMA instructions issued
-  // after the one a wait retires) are the same for all four combinations: 5 / 4 at phase 1
-  // (A split only), 4 at phase 3; tails retire everything.
-  constexpr bool AS = AKC, BS = BKC;
-#ifndef PZ_GEMM_QUAD4
-  if constexpr (AS) {
-    // Two sections per K-tile (A k-contiguous; B either way -- a k-strided B is read whole in section 0 through
-    // transposed loads): section 0 reads A region 0 and all of B (16 fragment loads) and runs quadrants
-    // (0,0), (0,1); section 1 reads A region 1 (8) and runs (1,1), (1,0).  32 MFMAs per section against the other row group's reads; the four-phase
-    // schedule below front-loads 12 of its 24 loads into one 16-MFMA phase, and its loads, not its DMA, set
-    // that phase's length (profiles/r05/feed_ab_*.log).  DMA: A1(kt+1) in section 0 (its region was last read
-    // in section 1 of kt-1), A0 | B0 | B1 (kt+2) in section 1 (last read in section 0 of kt).  Waits (2 DMA
-    // instructions per piece): section 0 retires A1(kt) (4 newer pieces), section 1 retires tile kt+1's
-    // section-0 pieces (4 newer, or only A1(kt+1) on the next-to-last tile); each is followed by the
-    // barrier the next reader of those regions passes.
-    issue(0, 0);
-    issue(1, 0);
-    issue(2, 0);
-    issue(3, 0);
-    if (nk > 1) {
-      issue(0, 1);
-      issue(1, 1);
-      issue(2, 1);
-      PZ_WAIT_VM(8);
-    } else {
-      PZ_WAIT_VM(2);
-    }
-    PZ_RAW_BARRIER();
-    if (wr == 1) PZ_RAW_BARRIER();  // stagger: row-1 waves run one barrier behind
-    for (int kt = 0; kt < nk; ++kt) {
-      const char* buf = smem + (kt & 1) * P8_BUF;
-      const bool n1 = kt + 1 < nk, n2 = kt + 2 < nk;
-      // section 0: quadrants (0,0), (0,1)
-      if (n1) issue(3, kt + 1);
-      read_a(buf, 0);
-      read_b(buf, 0);
-      read_b(buf, 1);
-      if (n1) PZ_WAIT_VM(8);
-      else PZ_WAIT_VM(0);
-      PZ_WAIT_LGKM0();
-      PZ_RAW_BARRIER();
-      mask_tail_a(kt);
-      mfma_quad(0, 0);
-      mfma_quad(0, 1);
-      PZ_RAW_BARRIER();
-      // section 1: quadrants (1,1), (1,0)
-      if (n2) {
-        issue(0, kt + 2);
-        issue(1, kt + 2);
-        issue(2, kt + 2);
-      }
-      read_a(buf, 1);
-      if (n2) PZ_WAIT_VM(8);
-      else if (n1) PZ_WAIT_VM(2);
-      PZ_WAIT_LGKM0();
-      PZ_RAW_BARRIER();
-      mask_tail_a(kt);
-      mfma_quad(1, 1);
-      mfma_quad(1, 0);
-      PZ_RAW_BARRIER();
-    }
-  } else
-#endif
-  {
-  if (AS) {
-    issue(0, 0);
-    issue(1, 0);
-    issue(2, 0);
-    issue(3, 0);
-    if (nk > 1) {
-      issue(0, 1);
-      issue(1, 1);
-      issue(2, 1);
-      PZ_WAIT_VM(8);
-    } else {
-      PZ_WAIT_VM(2);
-    }
+  // Two sections per K-tile (B either way -- a k-strided B is read whole in section 0 through transposed loads):
+  // section 0 reads A region 0 and all of B (16 fragment loads) and runs quadrants (0,0), (0,1); section 1 reads
+  // A region 1 (8) and runs (1,1), (1,0).  32 MFMAs per section against the other row group's reads; the older
+  // four-phase schedule front-loaded 12 of its 24 loads into one 16-MFMA phase, and its loads, not its DMA, set
+  // that phase's length (profiles/r05/feed_ab_*.log).  DMA: A1(kt+1) in section 0 (its region was last read
+  // in section 1 of kt-1), A0 | B0 | B1 (kt+2) in section 1 (last read in section 0 of kt).  Waits (2 DMA
+  // instructions per piece): section 0 retires A1(kt) (4 newer pieces), section 1 retires tile kt+1's
+  // section-0 pieces (4 newer, or only A1(kt+1) on the next-to-last tile); each is followed by the
+  // barrier the next reader of those regions passes.
+  issue(0, 0);
+  issue(1, 0);
+  issue(2, 0);
+  issue(3, 0);
+  if (nk > 1) {
+    issue(0, 1);
+    issue(1, 1);
+    issue(2, 1);
+    PZ_WAIT_VM(8);
   } else {
-    issue(1, 0);
-    issue(2, 0);
-    issue(0, 0);
-    issue(3, 0);
-    if (nk > 1) {
-      issue(1, 1);
-      issue(2, 1);
-      issue(0, 1);
-      issue(3, 1);
-      PZ_WAIT_VM(8);
-    } else {
-      PZ_WAIT_VM(0);
-    }
+    PZ_WAIT_VM(2);
   }
   PZ_RAW_BARRIER();
   if (wr == 1) PZ_RAW_BARRIER();  // stagger: row-1 waves run one barrier behind
-
   for (int kt = 0; kt < nk; ++kt) {
     const char* buf = smem + (kt & 1) * P8_BUF;
     const bool n1 = kt + 1 < nk, n2 = kt + 2 < nk;
-    // phase 0: quadrant (0,0)
-    if (AS && n1) issue(3, kt + 1);
+    // section 0: quadrants (0,0), (0,1)
+    if (n1) issue(3, kt + 1);
     read_a(buf, 0);
     read_b(buf, 0);
+    read_b(buf, 1);
+    if (n1) PZ_WAIT_VM(8);
+    else PZ_WAIT_VM(0);
     PZ_WAIT_LGKM0();
     PZ_RAW_BARRIER();
     mask_tail_a(kt);
     mfma_quad(0, 0);
-    PZ_RAW_BARRIER();
-    // phase 1: quadrant (0,1); (A split) retire A region 1 of this tile for phase 2
-    if (AS && n2) issue(0, kt + 2);
-    read_b(buf, 1);
-    if (AS) {
-      if (n2) PZ_WAIT_VM(10);
-      else if (n1) PZ_WAIT_VM(8);
-      else PZ_WAIT_VM(0);
-    }
-    PZ_WAIT_LGKM0();
-    PZ_RAW_BARRIER();
     mfma_quad(0, 1);
     PZ_RAW_BARRIER();
-    // phase 2: quadrant (1,1)
+    // section 1: quadrants (1,1), (1,0)
     if (n2) {
+      issue(0, kt + 2);
       issue(1, kt + 2);
-      if (!BS) issue(2, kt + 2);
+      issue(2, kt + 2);
     }
     read_a(buf, 1);
+    if (n2) PZ_WAIT_VM(8);
+    else if (n1) PZ_WAIT_VM(2);
     PZ_WAIT_LGKM0();
     PZ_RAW_BARRIER();
     mask_tail_a(kt);
     mfma_quad(1, 1);
-    PZ_RAW_BARRIER();
-    // phase 3: quadrant (1,0); retire tile kt+1's phase-0 operands (all of A when merged)
-    if (n2) {
-      if (BS) issue(2, kt + 2);
-      if (!AS) {
-        issue(0, kt + 2);
-        issue(3, kt + 2);
-      }
-    }
-    if (n2) PZ_WAIT_VM(8);
-    else if (n1) {
-      if (AS) PZ_WAIT_VM(2);
-      else PZ_WAIT_VM(0);
-    }
-    PZ_RAW_BARRIER();
     mfma_quad(1, 0);
     PZ_RAW_BARRIER();
-  }
   }
   if (wr == 0) PZ_RAW_BARRIER();
   if (F8 && p.rs) {  // per-row activation scale: lane rows m0 + wr*128 + 16 rb + (lane & 15)
@@ -1378,7 +1094,6 @@ __device__ __forceinline__ void gemm8p_body(const GemmP& p) {
     }
   }
 
-  if (p.dbg == 1) return;
   if (piece >= 0) {  // split tail: raw partial sums, summed + epilogued by gemm8p_tail_epilogue
     f32x4* W = reinterpret_cast<f32x4*>(p.ws) + (int64_t)piece * (32 * NT2);
 #pragma unroll
@@ -1606,7 +1321,7 @@ __global__ void __launch_bounds__(NT2, 1) gemm8k_kernel(GemmP p) {
 // Split tail, second pass: 16 blocks of 512 threads per leftover tile (one accumulator row-block rb and
 // one column half each, so the partial sums stream through many CUs); thread t sums the tail_s
 // partial accumulators it owned in gemm8p_kernel (fixed order) and applies the same epilogue.
-template <bool GEGLU, int PB = 8>
+template <bool GEGLU>
 __global__ void __launch_bounds__(NT2) gemm8p_tail_epilogue(GemmP p) {
   const int tile = blockIdx.x >> 4, rb = (blockIdx.x >> 1) & 7, h = blockIdx.x & 1;
   int tm, tn;
@@ -1616,6 +1331,7 @@ __global__ void __launch_bounds__(NT2) gemm8p_tail_epilogue(GemmP p) {
   // GeGLU pairs gate cb = h with up cb = h + 2; plain outputs take cb = 2h, 2h + 1
   const int c0 = GEGLU ? h : 2 * h, c1 = GEGLU ? h + 2 : 2 * h + 1;
   // pieces loaded PB at a time (2 PB loads in flight per thread), summed in piece order (deterministic)
+  constexpr int PB = 8;
   const f32x4* W0 = W + (rb * 4 + c0) * NT2 + t;
   const f32x4* W1 = W + (rb * 4 + c1) * NT2 + t;
   auto sum_pieces = [&](f32x4& a0, f32x4& a1) {
@@ -1909,21 +1625,6 @@ static int launch_tile_x(const GemmP& p, hipStream_t st) {
   return PZ_OK;
 }
 
-template <bool AKC, bool BKC, bool GEGLU>
-static int launch256(const GemmP& p, int64_t batch, hipStream_t st) {
-  const int smem = 2 * 2 * 256 * 64 * 2;  // 128 KiB for either pipeline
-  auto kern = gemm256_kernel<AKC, BKC, GEGLU, BK256>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n, (unsigned)batch), dim3(NT2), smem, st, p);
-  PZ_CHECK_LAUNCH();
-  return PZ_OK;
-}
-
-static bool use_8phase();
 static bool use_khalf(bool akc, bool bkc, int64_t m, int64_t n, int64_t k);
 
 namespace {
@@ -1996,7 +1697,7 @@ void plan_tail(Plan& pl, const pz_gemm_args* a) {
   }
   // no split below 8 K-tiles: a piece writes (and the merge re-reads) a 256 KiB fp32 partial, which a short
   // reduction cannot amortise -- the K = 320 action-expert wgrad (8192 x 1024, 5 K-tiles) took 42.0 us with
-  // 2 pieces per leftover tile vs 20.0 us whole (tools/shape_ab.py, profiles/r03/shape_ab.log)
+  // 2 pieces per leftover tile vs 20.0 us whole (profiles/r03/shape_ab.log)
   s = s < nk / 2 ? s : nk / 2;
   if (s < 2 || nk < 8) return;
   const int64_t kt = (nk + s - 1) / s;
@@ -2007,20 +1708,19 @@ void plan_tail(Plan& pl, const pz_gemm_args* a) {
   pl.tail_kt = (int)kt;
 }
 
-// row-slab kernel (64 < M <= PZ_ROWS_MAXM, default 512; k-contiguous A and B, batch 1, forward
+// row-slab kernel (64 < M <= ROWS_MAXM; k-contiguous A and B, batch 1, forward
 // epilogues): whole-K 64-row tiles, 16 / 32 / 64 columns wide so the tiles cover >= 128 workgroups;
 // 8 waves split K when it has >= 16 chunks (4 for GeGLU).  Taken where it measured faster than the
 // 128-tile + split-K pair or the 256-tile kernel (tools/rows_bench.py, profiles/r03/rows_bench.log):
 // K <= 2048 and <= 4096 output columns -- B = 1 SigLIP q|k|v 20.9 -> 12.0 us, o 14.6 -> 9.0 us, Gemma
 // q|k|v / o at 276 rows 19.8 -> 18.1 us, action expert (320 rows) q|k|v 17.5 -> 11.0, o 16.0 -> 13.4,
 // gate|up + GeGLU 32.9 -> 25.8 us; the long-K / wide ones (SigLIP fc1 / fc2, 4096-K down projections,
-// the 32768-wide Gemma gate|up) stay on the tile kernels.  PZ_GEMM_ROWS=0: never; =1: any 64 < M <= maxm
+// the 32768-wide Gemma gate|up) stay on the tile kernels.  PZ_GEMM_ROWS=0: never; =1: any 64 < M <= ROWS_MAXM
 // (A/B runs; read per call)
+constexpr int64_t ROWS_MAXM = 1024;  // (C5's 768 / 789 prefill rows: 21.32 vs 21.52 ms at 512)
 bool plan_rows(Plan& pl, const pz_gemm_args* a, int64_t ncols) {
   const char* er = getenv("PZ_GEMM_ROWS");
-  const char* em = getenv("PZ_ROWS_MAXM");
-  const int64_t maxm = em ? atoll(em) : 1024;  // (C5's 768 / 789 prefill rows: 21.32 vs 21.52 ms at 512)
-  if ((er && er[0] == '0') || a->M <= 64 || a->M > maxm || !pl.akc || !pl.bkc || a->batch != 1 ||
+  if ((er && er[0] == '0') || a->M <= 64 || a->M > ROWS_MAXM || !pl.akc || !pl.bkc || a->batch != 1 ||
       a->epilogue >= PZ_EPI_DGELU || a->norm_w)
     return false;
   if (!(er && er[0] == '1') && (a->K > 2048 || ncols > 4096)) return false;
@@ -2061,17 +1761,15 @@ bool plan_tall(Plan& pl, const pz_gemm_args* a, int64_t ncols) {
   if (!(e && e[0] == '1') &&
       !(a->M <= 320 && pl.bkc && !pl.geglu && a->K >= 4300 && ncols <= 2048))
     return false;
-#ifndef PZ_TALL_AB
-  if (!pl.bkc || pl.geglu) return false;  // only the plain k-contiguous form is built (pz_gemm_tall.hip)
-#endif
-  if (!pl.akc || (!pl.bkc && pl.geglu) || a->batch != 1 || a->fp8_mode != 0 || a->norm_w || a->epilogue >= PZ_EPI_DGELU ||
+  if (!pl.bkc || pl.geglu) return false;  // plain k-contiguous B only (pz_gemm_tall.hip)
+  if (!pl.akc || a->batch != 1 || a->fp8_mode != 0 || a->norm_w || a->epilogue >= PZ_EPI_DGELU ||
       a->M <= 64 || a->M > 1024 || a->K % 8 != 0)
     return false;
   const int64_t t5 = (a->M + 319) / 320, t4 = (a->M + 255) / 256;
   pl.tall_mi = t5 * 320 <= t4 * 256 ? 5 : 4;
   pl.tiles_m = pl.tall_mi == 5 ? t5 : t4;
   pl.tiles_n = (ncols + 63) / 64;
-  const int64_t bkt = pl.geglu ? 32 : 64;
+  const int64_t bkt = 64;
   const int64_t nk = (a->K + bkt - 1) / bkt;
   const int64_t units = pl.tiles_m * pl.tiles_n;
   int64_t S = (256 + units - 1) / units;
@@ -2080,7 +1778,7 @@ bool plan_tall(Plan& pl, const pz_gemm_args* a, int64_t ncols) {
   if (S >= 2) {
     const int64_t per = (nk + S - 1) / S;
     const int64_t Se = (nk + per - 1) / per;
-    const int64_t ldw = pl.geglu ? 2 * a->geglu_inter : (a->N + 3) / 4 * 4;
+    const int64_t ldw = (a->N + 3) / 4 * 4;
     if (Se >= 2 && a->workspace && PZ_ALIGNED(a->workspace, 16) && Se * a->M * ldw * 4 <= a->ws_bytes) {
       pl.splits = (int)Se;
       pl.ksplit = per * bkt;
@@ -2095,10 +1793,11 @@ bool plan_tall(Plan& pl, const pz_gemm_args* a, int64_t ncols) {
 // skinny-64 split-K combined in the launch: S tile-private [64][nc] fp32 slabs per tile fit the workspace (bf16 C,
 // forward epilogue)
 static bool sk64_fits(const Plan& pl, const pz_gemm_args* a) {
-  const int64_t tiles = pl.tiles_n * ((a->M + 63) / 64);
-  return (int64_t)pl.splits * tiles * 64 * pl.skinny_nc * 4 <= a->ws_bytes && !a->c_fp32 &&
+  return (int64_t)pl.splits * pl.tiles_n * 64 * pl.skinny_nc * 4 <= a->ws_bytes && !a->c_fp32 &&
          a->epilogue < PZ_EPI_DGELU;
 }
+
+constexpr int64_t MIN_UNITS_256 = 160;  // workgroups the 256-tile path must reach to be taken
 
 Plan make_plan(const pz_gemm_args* a) {
   Plan pl{};
@@ -2111,7 +1810,7 @@ Plan make_plan(const pz_gemm_args* a) {
   if (a->K2 > 0) {
     const int64_t cwx = pl.geglu ? BT / 2 : BT;
     const int64_t tm = (a->M + BT - 1) / BT, tn = (ncols + cwx - 1) / cwx;
-    if (use_8phase() && pl.akc && a->K % 8 == 0 && a->M >= 512 && ncols >= (pl.geglu ? 256 : 512) && tm * tn >= 160) {
+    if (pl.akc && a->K % 8 == 0 && a->M >= 512 && ncols >= (pl.geglu ? 256 : 512) && tm * tn >= 160) {
       pl.kind = PATH_256;
       pl.tiles_m = tm;
       pl.tiles_n = tn;
@@ -2125,10 +1824,9 @@ Plan make_plan(const pz_gemm_args* a) {
   }
   // fp8 W8A8: the 8-phase 256-tile kernel on code pairs (K, lda, ldb halved by the caller of make_plan); the row-slab
   // shapes (64 < M <= 1024, <= 2048 codes of K in 128-code chunks, <= 4096 columns, no GeGLU: C5's prefill q|k|v / o)
-  // take the W8A8 row-slab kernel (PZ_ROWS_W8A8=0: the 8-phase kernel, A/B; read per call)
+  // take the W8A8 row-slab kernel
   if (a->fp8_mode == 1) {
-    const char* er8 = getenv("PZ_ROWS_W8A8");
-    if (!(er8 && er8[0] == '0') && !pl.geglu && a->M > 64 && a->M <= 1024 && a->K % 64 == 0 && a->K <= 1024 &&
+    if (!pl.geglu && a->M > 64 && a->M <= 1024 && a->K % 64 == 0 && a->K <= 1024 &&
         ncols <= 4096 && a->a_row_scale) {
       const int64_t tm = (a->M + 63) / 64;
       int tnb = 4;
@@ -2149,20 +1847,16 @@ Plan make_plan(const pz_gemm_args* a) {
     return pl;
   }
   // skinny-64 path: 16 < M <= 64 rows (bf16), or any M <= 64 with fp8 weights (W8A16)
-  // rows 65..PZ_SK64_MAXM run as 64-row chunks of the same kernel (blockIdx.y)
-  const char* emax = getenv("PZ_SK64_MAXM");
-  const int64_t sk_maxm = emax ? atoll(emax) : 64;
-  const bool sk64_ok = (a->M <= 64 || a->M <= sk_maxm) && pl.akc && pl.bkc && a->K % 64 == 0 && a->batch == 1 &&
+  const bool sk64_ok = a->M <= 64 && pl.akc && pl.bkc && a->K % 64 == 0 && a->batch == 1 &&
                        !a->c_fp32 && a->epilogue < PZ_EPI_DGELU;
-  const char* e64 = getenv("PZ_SK64");  // "0": rows 17..64 take the tile kernels (A/B; read per call)
   if (a->fp8_mode == 2 && a->M > 64) {  // W8A16 above 64 rows: the row-slab kernel or nothing (pz_gemm rejects)
     pl.kind = PATH_SKINNY64;
     plan_rows(pl, a, ncols);
     return pl;
   }
-  if (a->fp8_mode == 2 || (sk64_ok && a->M > 16 && !(e64 && e64[0] == '0'))) {
+  if (a->fp8_mode == 2 || (sk64_ok && a->M > 16)) {
     pl.kind = PATH_SKINNY64;
-    pl.skinny_mb = a->M > 64 ? 4 : (int)((a->M + 15) / 16);
+    pl.skinny_mb = (int)((a->M + 15) / 16);
     pl.skinny_mb = pl.skinny_mb == 3 ? 4 : pl.skinny_mb;
     // 16 real columns per block, 8 waves: every block re-reads the (L2-resident) activation rows, so
     // narrower blocks multiply that traffic -- measured at 50 rows (tools/skinny_bench.py): q|k|v
@@ -2170,19 +1864,16 @@ Plan make_plan(const pz_gemm_args* a) {
     pl.skinny_w = a->K / 64 >= 8 ? 8 : 4;
     pl.skinny_nc = 16;
     // narrow outputs (o / down projections: 64 blocks of 16 columns) split K over blockIdx.z so the
-    // weight stream spreads over ~256 workgroups; partials summed by splitk_epilogue_kernel
-    // (PZ_SK64_SPLIT = 0 disables; no fused norm / GeGLU with a split)
+    // weight stream spreads over ~256 workgroups; partials summed in the launch or by splitk_epilogue_kernel
+    // (no fused norm / GeGLU with a split)
     {
-      const char* es = getenv("PZ_SK64_SPLIT");
-      const int64_t nblk = (ncols + 15) / 16 * ((a->M + 63) / 64);
+      const int64_t nblk = (ncols + 15) / 16;
       const int64_t kch = a->K / 64;
-      if (!(es && es[0] == '0') && !a->norm_w && !pl.geglu && a->workspace && nblk < 128 &&
+      if (!a->norm_w && !pl.geglu && a->workspace && nblk < 128 &&
           kch >= 16) {
         int64_t S = (256 + nblk - 1) / nblk;
         S = S < kch / 8 ? S : kch / 8;
         S = S < 8 ? S : 8;
-        const char* esn = getenv("PZ_SK64_S");  // A/B override of the slice count (read per call)
-        if (esn && atoi(esn) >= 2 && atoi(esn) <= 8 && atoi(esn) <= kch / 4) S = atoi(esn);
         const int64_t ldw = (a->N + 3) / 4 * 4;
         if (S >= 2 && S * a->M * ldw * 4 <= a->ws_bytes && PZ_ALIGNED(a->workspace, 16)) {
           const int64_t per = (kch + S - 1) / S;
@@ -2191,12 +1882,6 @@ Plan make_plan(const pz_gemm_args* a) {
           pl.ldw = ldw;
         }
       }
-    }
-    {  // A/B overrides (read per call): PZ_SK64_NC = 4|8|16 columns per block, PZ_SK64_W = 4|8 waves
-      const char* e = getenv("PZ_SK64_NC");
-      if (e && (atoi(e) == 4 || atoi(e) == 8 || atoi(e) == 16)) pl.skinny_nc = atoi(e);
-      e = getenv("PZ_SK64_W");
-      if (e && (atoi(e) == 4 || atoi(e) == 8)) pl.skinny_w = atoi(e);
     }
     pl.tiles_n = (ncols + pl.skinny_nc - 1) / pl.skinny_nc;
     return pl;
@@ -2234,32 +1919,28 @@ Plan make_plan(const pz_gemm_args* a) {
   }
   // rows from which the 256-tile kernels are tried: 256 for the GeGLU GEMM and long-K GEMMs (prefill
   // at B=1, 276 rows: 64 vs 78 us and 51 vs 56 us measured), 512 otherwise (narrow prefill GEMMs
-  // are faster on 128-row tiles); PZ_GEMM_256_MINM overrides (A/B runs)
-  const char* mm = getenv("PZ_GEMM_256_MINM");
-  const int64_t min_m = mm ? atoll(mm) : ((pl.geglu || a->K >= 8192 || (a->batch > 1 && !pl.akc && !pl.bkc)) ? 256 : 512);
+  // are faster on 128-row tiles)
+  const int64_t min_m = (pl.geglu || a->K >= 8192 || (a->batch > 1 && !pl.akc && !pl.bkc)) ? 256 : 512;
   // at most half a round of 256-tiles at short K (the action expert's 1024- and 1280-row GEMMs at micro-batch 256): the 128-tile
   // kernel (+ split-K) beats the 256-tile split tail, 22-37 vs 29-45 us per launch, except at K 8192
-  // (tools/attn_gemm_ab.py, profiles/r05/attn_gemm_ab.log); PZ_GEMM_SMALL256=1 keeps the 256 path (A/B)
-  const char* es2 = getenv("PZ_GEMM_SMALL256");
+  // (profiles/r05/attn_gemm_ab.log)
   const bool small_short = !pl.geglu && a->batch == 1 && a->M >= 1024 && a->K <= 4096 &&
-                           ((a->M + BT - 1) / BT) * ((ncols + cw - 1) / cw) <= 128 && !(es2 && es2[0] == '1');
+                           ((a->M + BT - 1) / BT) * ((ncols + cw - 1) / cw) <= 128;
   // batched TN GEMMs with >= 256 x 256 outputs per batch entry (the joint attention's dK = dS^T Q and dV = P^T dO,
   // 288 x 256 per sample): the 256-tile kernel, two row tiles per sample, 173 vs 190-203 us (dV of the 5-row action
-  // mixture 28.7 vs 40.6 us) against the 128-tile kernel (tools/attn_gemm_ab.py, profiles/r05/attn_gemm_ab_r5s.log)
+  // mixture 28.7 vs 40.6 us) against the 128-tile kernel (profiles/r05/attn_gemm_ab_r5s.log)
   const bool batched_tn = a->batch > 1 && !pl.akc && !pl.bkc && a->M >= 256 && ncols >= 256;
-  const char* mn = getenv("PZ_GEMM_256_MINN");  // A/B: output columns from which the 256-tile path is tried
-  const int64_t min_n = mn ? atoll(mn) : (pl.geglu || batched_tn ? 256 : 512);
-  if ((use_8phase() ? a->K % 8 == 0 : a->K % BK256 == 0) && a->M >= min_m && ncols >= min_n && !small_short) {
+  const int64_t min_n = pl.geglu || batched_tn ? 256 : 512;  // output columns from which the 256-tile path is tried
+  if (a->K % 8 == 0 && a->M >= min_m && ncols >= min_n && !small_short) {
     const int64_t tm = (a->M + BT - 1) / BT, tn = (ncols + cw - 1) / cw;
     Plan cand = pl;
     cand.kind = PATH_256;
     cand.tiles_m = tm;
     cand.tiles_n = tn;
-    if (use_8phase()) plan_tail(cand, a);
+    plan_tail(cand, a);
     // enough workgroups to fill the chip: whole tiles, or tiles split into K-pieces
     const int64_t units = cand.tail_s ? cand.dp_tiles + (tm * tn - cand.dp_tiles) * cand.tail_s : a->batch * tm * tn;
-    const char* mu = getenv("PZ_GEMM_256_MINUNITS");  // A/B: workgroups the 256-tile path must reach
-    if (units >= (mu ? atoll(mu) : 160)) return cand;
+    if (units >= MIN_UNITS_256) return cand;
   }
   if (plan_rows(pl, a, ncols)) return pl;
   pl.kind = PATH_TILE;
@@ -2270,8 +1951,7 @@ Plan make_plan(const pz_gemm_args* a) {
   // split-K when one 128x128 tile per WG leaves most of the 256 CUs idle
   const int64_t tiles = pl.tiles_m * pl.tiles_n;
   const int64_t nk = (a->K + BK - 1) / BK;
-  const char* esk = getenv("PZ_SPLITK");  // "0": whole-K tiles only (A/B; read per call)
-  if (a->batch == 1 && a->workspace && tiles < 120 && nk >= 4 && !(esk && esk[0] == '0')) {
+  if (a->batch == 1 && a->workspace && tiles < 120 && nk >= 4) {
     int64_t S = (240 + tiles - 1) / tiles;
     S = S < 16 ? S : 16;
     S = S < nk / 2 ? S : nk / 2;
@@ -2320,16 +2000,13 @@ extern "C" const char* pz_gemm_kernel_name(const pz_gemm_args* a) {
     case PATH_256:
       if (a->K2 > 0)
         snprintf(buf, sizeof(buf), "gemm8p_x_kernel<%s, %s, %s>", bstr(pl.akc), bstr(pl.bkc), bstr(pl.geglu));
-      else if (use_8phase() && pl.tail_s)
+      else if (pl.tail_s)
         snprintf(buf, sizeof(buf), "%s<%s, %s, %s, %s>+gemm8p_tail_epilogue(tail %lld x %d)",
                  use_khalf(pl.akc, pl.bkc, a->M, a->N, a->K) ? "gemm8k_kernel" : "gemm8p_kernel", bstr(pl.akc), bstr(pl.bkc), bstr(pl.geglu), bstr(a->K % 64 != 0),
                  (long long)(pl.tiles_m * pl.tiles_n - pl.dp_tiles), pl.tail_s);
-      else if (use_8phase())
+      else
         snprintf(buf, sizeof(buf), "%s<%s, %s, %s, %s>", use_khalf(pl.akc, pl.bkc, a->M, a->N, a->K) ? "gemm8k_kernel" : "gemm8p_kernel",
                  bstr(pl.akc), bstr(pl.bkc), bstr(pl.geglu), bstr(a->K % 64 != 0));
-      else
-        snprintf(buf, sizeof(buf), "gemm256_kernel<%s, %s, %s, %d>", bstr(pl.akc), bstr(pl.bkc), bstr(pl.geglu),
-                 BK256);
       break;
     case PATH_TILE:
       if (a->K2 > 0) snprintf(buf, sizeof(buf), "gemm_x_kernel<%s, %s, %d>", bstr(pl.akc), bstr(pl.bkc), pl.wm);
@@ -2342,9 +2019,8 @@ extern "C" const char* pz_gemm_kernel_name(const pz_gemm_args* a) {
         snprintf(buf, sizeof(buf), "gemm_rows_kernel<%d, %d, %d, %s, %s>", pl.rows_w, pl.rows_tmb, pl.rows_tnb,
                  bstr(pl.geglu), bstr(pl.rows_f8 == 1));
       break;
-    case PATH_TALL:
-      snprintf(buf, sizeof(buf), "gemm_tall_kernel<%d, %d, %d, %d, %s, %s>%s", pl.tall_mi, pl.geglu ? 4 : 2,
-               pl.geglu ? 32 : 64, pl.geglu ? 4 : 3, bstr(pl.geglu), bstr(pl.bkc),
+    case PATH_TALL:  // (the label keeps the two flags of the retired GeGLU / k-strided-B forms: profile logs key on it)
+      snprintf(buf, sizeof(buf), "gemm_tall_kernel<%d, 2, 64, 3, false, true>%s", pl.tall_mi,
                pl.splits > 1 ? "+splitk_epilogue_kernel" : "");
       break;
     case PATH_SPLIT:
@@ -2377,7 +2053,7 @@ static int launch8p_f8(const GemmP& p, hipStream_t st) {
   hipLaunchKernelGGL(kern, dim3(units, 1), dim3(NT2), smem, st, p);
   PZ_CHECK_LAUNCH();
   if (p.tail_s) {
-    launch_tail<GEGLU>(p, T, st);
+    hipLaunchKernelGGL(gemm8p_tail_epilogue<GEGLU>, dim3((T - p.dp_tiles) * 16), dim3(NT2), 0, st, p);
     PZ_CHECK_LAUNCH();
   }
   return PZ_OK;
@@ -2417,33 +2093,19 @@ static int launch_tile_any(GemmP& p, const Plan& pl, int64_t batch, hipStream_t 
 // >= 4096 output columns or a reduction >= 4096: 2-4 % faster there, 2.5 % slower at 2048 x 2048
 // (profiles/r05/nn_main_ab.log; smaller row counts not measured, left on the k-half kernel).  Micro-batch census:
 // gate|up dgrad 128.5 vs 136.2 ms, down-proj DGEGLU dgrad 90.5 vs 94.1 ms, all GEMMs 854.6 vs 865.5 ms
-// (profiles/r05/census_nn_routing_ab.log; -DPZ_NN_KHALF builds the old routing for that A/B).
-// PZ_GEMM_MAIN=quad|khalf forces one (A/B runs; read per call).
+// (profiles/r05/census_nn_routing_ab.log).
 static bool use_khalf(bool akc, bool bkc, int64_t m, int64_t n, int64_t k) {
-  const char* e = getenv("PZ_GEMM_MAIN");
-  if (e && strcmp(e, "quad") == 0) return false;
-  if (e && strcmp(e, "khalf") == 0) return true;
-#ifndef PZ_NN_KHALF
   if (akc && !bkc && m >= 16384 && (n >= 4096 || k >= 4096)) return false;
-#endif
   return !(akc && bkc);
-}
-
-// split-tail merge; PZ_TAIL_PB = 4 | 8 partial pieces loaded per round (A/B; read per call)
-template <bool GEGLU>
-static void launch_tail(const GemmP& p, int T, hipStream_t st) {
-  const char* e = getenv("PZ_TAIL_PB");
-  if (e && atoi(e) == 4)
-    hipLaunchKernelGGL((gemm8p_tail_epilogue<GEGLU, 4>), dim3((T - p.dp_tiles) * 16), dim3(NT2), 0, st, p);
-  else
-    hipLaunchKernelGGL((gemm8p_tail_epilogue<GEGLU, 8>), dim3((T - p.dp_tiles) * 16), dim3(NT2), 0, st, p);
 }
 
 template <bool AKC, bool BKC, bool GEGLU, bool KTAIL>
 static int launch8p_k(const GemmP& p, int64_t batch, hipStream_t st) {
   const int smem = 2 * P8_BUF;  // 128 KiB
   const bool kh = use_khalf(AKC, BKC, p.M, p.N, p.K);
-  auto kern = kh ? gemm8k_kernel<AKC, BKC, GEGLU, KTAIL> : gemm8p_kernel<AKC, BKC, GEGLU, KTAIL>;
+  auto kern = gemm8k_kernel<AKC, BKC, GEGLU, KTAIL>;
+  if constexpr (AKC)  // (gemm8p_kernel reads a k-contiguous A only; use_khalf never sends a k-strided A there)
+    if (!kh) kern = gemm8p_kernel<AKC, BKC, GEGLU, KTAIL>;
   static bool attr_set[2] = {false, false};
   if (!attr_set[kh]) {
     hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
@@ -2454,7 +2116,7 @@ static int launch8p_k(const GemmP& p, int64_t batch, hipStream_t st) {
   hipLaunchKernelGGL(kern, dim3(units, (unsigned)batch), dim3(NT2), smem, st, p);
   PZ_CHECK_LAUNCH();
   if (p.tail_s) {
-    launch_tail<GEGLU>(p, T, st);
+    hipLaunchKernelGGL(gemm8p_tail_epilogue<GEGLU>, dim3((T - p.dp_tiles) * 16), dim3(NT2), 0, st, p);
     PZ_CHECK_LAUNCH();
   }
   return PZ_OK;
@@ -2479,12 +2141,6 @@ static int launch8p_x(const GemmP& p, hipStream_t st) {
   hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n, 1), dim3(NT2), smem, st, p);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
-}
-
-// large-GEMM kernel: the 8-phase ping-pong (default) or the 2-stage 256 kernel (PZ_GEMM_BIG=2stage, A/B runs)
-static bool use_8phase() {
-  const char* e = getenv("PZ_GEMM_BIG");  // read per call: A/B runs flip it in-process
-  return !(e && strcmp(e, "2stage") == 0);
 }
 
 extern "C" int pz_gemm(const pz_gemm_args* a, void* stream) {
@@ -2587,14 +2243,6 @@ extern "C" int pz_gemm(const pz_gemm_args* a, void* stream) {
     p.B2 = (const bf16_t*)a->B2;
     p.lda2 = a->lda2; p.ldb2 = a->ldb2; p.K2 = a->K2;
   }
-  {
-    const char* e = getenv("PZ_GEMM_DBG");
-    p.dbg = e ? atoi(e) : 0;
-    e = getenv("PZ_GEMM_NT");
-    p.nt_store = e ? atoi(e) : 0;
-    e = getenv("PZ_GEMM_NT_AUX");
-    p.nt_aux = p.nt_store || (e && atoi(e) != 0);
-  }
   hipStream_t st = (hipStream_t)stream;
 
   const Plan pl = make_plan(a);
@@ -2622,7 +2270,7 @@ extern "C" int pz_gemm(const pz_gemm_args* a, void* stream) {
       // in-launch combine: S tile-private [64][nc] fp32 slabs per tile, bf16 C with a forward epilogue
       p.sk_tk = sk64_fits(pl, a) ? 0 : -1;
     }
-    return pz_sk64_launch(p, pl.skinny_w, pl.skinny_nc, pl.skinny_mb, a->fp8_mode == 2, pl.tiles_n, st);
+    return pz_sk64_launch(p, pl.skinny_w, pl.skinny_mb, a->fp8_mode == 2, pl.tiles_n, st);
   }
   if (a->fp8_mode == 1 && pl.kind == PATH_ROWS) {  // W8A8 row slab
     p.tiles_m = (int)pl.tiles_m;
@@ -2659,7 +2307,7 @@ extern "C" int pz_gemm(const pz_gemm_args* a, void* stream) {
       p.ksplit = pl.ksplit;
       p.ldw = pl.ldw;
     }
-    return pz_tall_launch(p, pl.tall_mi, geglu, pl.bkc, pl.splits > 1 ? pl.splits : 1, st);
+    return pz_tall_launch(p, pl.tall_mi, pl.splits > 1 ? pl.splits : 1, st);
   }
   if (a->K2 > 0) {
     if (pl.kind == PATH_256) {
@@ -2672,7 +2320,7 @@ extern "C" int pz_gemm(const pz_gemm_args* a, void* stream) {
     if (!a->a_kcontig && a->b_kcontig) return launch_tile_x<false, true, 2>(p, st);
     return launch_tile_x<false, false, 2>(p, st);
   }
-  if (pl.kind == PATH_256 && use_8phase()) {
+  if (pl.kind == PATH_256) {
     if (pl.tail_s) {
       p.ws = (float*)a->workspace;
       p.dp_tiles = pl.dp_tiles;
@@ -2687,16 +2335,6 @@ extern "C" int pz_gemm(const pz_gemm_args* a, void* stream) {
     if (a->a_kcontig && !a->b_kcontig) return launch8p<true, false, false>(p, a->batch, st);
     if (!a->a_kcontig && a->b_kcontig) return launch8p<false, true, false>(p, a->batch, st);
     return launch8p<false, false, false>(p, a->batch, st);
-  }
-  if (pl.kind == PATH_256) {
-    if (geglu) {
-      if (a->a_kcontig) return launch256<true, true, true>(p, a->batch, st);
-      return launch256<false, true, true>(p, a->batch, st);
-    }
-    if (a->a_kcontig && a->b_kcontig) return launch256<true, true, false>(p, a->batch, st);
-    if (a->a_kcontig && !a->b_kcontig) return launch256<true, false, false>(p, a->batch, st);
-    if (!a->a_kcontig && a->b_kcontig) return launch256<false, true, false>(p, a->batch, st);
-    return launch256<false, false, false>(p, a->batch, st);
   }
   if (pl.kind == PATH_SPLIT) {
     p.ws = (float*)a->workspace;
@@ -2775,9 +2413,9 @@ extern "C" int pz_gemm_qkv_rope(const pz_qkv_rope_args* a, void* stream) {
     p.rk = (bf16_t*)a->k_out;
     p.rv = (bf16_t*)a->v_out;
     p.rT = a->T; p.rnh = a->nh; p.rLq = a->Lq; p.rqoff = a->qoff; p.rLk = a->Lk; p.rkoff = a->koff;
-    return pz_sk64_launch(p, pl.skinny_w, 16, pl.skinny_mb, a->w_fp8 != 0, a->N / 16, (hipStream_t)stream);
+    return pz_sk64_launch(p, pl.skinny_w, pl.skinny_mb, a->w_fp8 != 0, a->N / 16, (hipStream_t)stream);
   }
-  if (a->norm_w || a->w_fp8 || !use_8phase() || pl.kind != PATH_256) return PZ_ERR_UNSUPPORTED;
+  if (a->norm_w || a->w_fp8 || pl.kind != PATH_256) return PZ_ERR_UNSUPPORTED;
   GemmP p;
   memset(&p, 0, sizeof(p));
   p.group = 8;

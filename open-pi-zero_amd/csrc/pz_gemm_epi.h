@@ -36,9 +36,6 @@ struct GemmP {
   float neps;
   // fp8 W8A8 (gemm8p_f8_kernel): per-row activation scales [M] or NULL
   const float* rs;
-  // measurement knob (PZ_GEMM_DBG, read per call): 1 = the 8-phase kernels skip their epilogue stores
-  // (tools/epi_probe.py: main-loop time alone); 0 in every product run
-  int dbg;
   // fused q|k|v RoPE epilogue (pz_gemm_qkv_rope; 8-phase kernel, head_dim 256 = one column tile per head):
   // the bf16-rounded projection of head n0/256 is rotated at rpos[m] (table rcs) and scattered into the
   // joint Q / K / V buffers like pz_qkv_rope_split; C is not written.  rcs == NULL: off.
@@ -46,11 +43,6 @@ struct GemmP {
   const float* rcs;
   bf16_t *rq, *rk, *rv;
   int64_t rT, rnh, rLq, rqoff, rLk, rkoff;
-  // 8-phase LDS-staged epilogues: non-temporal (streaming) 16-B output stores (PZ_GEMM_NT, read per call)
-  int nt_store;
-  // ... and for the saved activations only (aux: GeGLU g|u, GELU / SiLU pre-activation -- read again only by the
-  // backward, long after; PZ_GEMM_NT_AUX, read per call)
-  int nt_aux;
   // super-row height of the 8-phase kernels' tile order (tile_coords; PZ_GEMM_GROUP, read per call; default 8)
   int group;
   // rank extension (ABI 22; LoRA adapters): acc += sum_{j < K2} A2(m, j) B2(j, n) with the k-contiguity of A / B,
@@ -350,11 +342,11 @@ __device__ __forceinline__ void store_geglu4(const GemmP& p, int64_t cofs, int64
 }  // namespace
 // row-slab GEMM launcher (pz_gemm_rows.hip): w waves, tnb 16-column blocks per 64-row tile
 int pz_rows_launch(const GemmP& p, int w, int tnb, bool geglu, int f8w, hipStream_t st);
-// skinny-64 GEMM launcher (pz_gemm_rows.hip): 16 < M <= 64 rows (and fp8-weight W8A16), w waves, nc columns
-// per block, mb 16-row blocks
-int pz_sk64_launch(const GemmP& p, int w, int nc, int mb, bool f8w, int64_t tiles_n, hipStream_t st);
-// tall-tile GEMM launcher (pz_gemm_tall.hip): 64 * mi rows per tile, k-contiguous A, B k-contiguous or (plain
-// epilogues) k-strided, split-K over blockIdx.y when splits > 1
-int pz_tall_launch(const GemmP& p, int mi, bool geglu, bool bkc, int splits, hipStream_t st);
+// skinny-64 GEMM launcher (pz_gemm_rows.hip): M <= 64 rows (16 < M bf16, any with fp8 weights: W8A16), w waves,
+// 16 columns per block, mb 16-row blocks
+int pz_sk64_launch(const GemmP& p, int w, int mb, bool f8w, int64_t tiles_n, hipStream_t st);
+// tall-tile GEMM launcher (pz_gemm_tall.hip): 64 * mi rows per tile, k-contiguous A and B, plain epilogues,
+// split-K over blockIdx.y when splits > 1
+int pz_tall_launch(const GemmP& p, int mi, int splits, hipStream_t st);
 // split-K second pass (pz_gemm.hip): C = epilogue(sum of the S fp32 partial slabs in p.ws)
 int pz_splitk_epi_launch(const GemmP& p, int S, hipStream_t st);

@@ -334,7 +334,7 @@ __global__ void __launch_bounds__(W * 64) gemm_skinny64_kernel(GemmP p) {
   const int64_t nr = rope ? (int64_t)(blockIdx.x >> 4) * 256 + (blockIdx.x & 15) * 8 + (lane & 7) + ((lane & 8) << 4)
                           : n0 + (lane & 15) % NC;
   const bool nok = nr < ncols;
-  // row chunks of 64 (blockIdx.y): M > 64 runs as independent 64-row problems sharing the weights in L2
+  // row chunks of 64 (blockIdx.y; the launcher passes M <= 64: one chunk)
   const int64_t row0 = (int64_t)blockIdx.y * 64;
   const int64_t Mc = min((int64_t)64, p.M - row0);
   constexpr int ES = F8W ? 1 : 2;  // weight element bytes
@@ -606,46 +606,38 @@ int pz_rows_launch(const GemmP& p, int w, int tnb, bool geglu, int f8w, hipStrea
   return w == 8 ? launch_rows_w<8>(p, tnb, geglu, st) : launch_rows_w<4>(p, tnb, geglu, st);
 }
 
-template <int W, int NC, int MB, bool F8W>
+// M <= 64 rows (one 64-row chunk), 16 columns per block
+template <int W, int MB, bool F8W>
 static int launch_sk64(const GemmP& p0, int64_t tiles_n, hipStream_t st) {
   GemmP p = p0;
   const int S = p.ksplit > 0 ? (int)((p.K / 64 + p.ksplit / 64 - 1) / (p.ksplit / 64)) : 1;
-  const int64_t tiles = tiles_n * ((p.M + 63) / 64);
   // in-launch combine (PZ_SK64_FUSED=0: the two-launch form, A/B; read per call): each launch gets its own range
   // of arrival counters, dealt round-robin in 256-counter steps (256 launches in flight before a range is reused)
   const char* e = getenv("PZ_SK64_FUSED");
   const bool fits = p.sk_tk >= 0;  // (pz_gemm: the tile-private slabs fit the workspace, forward bf16 epilogue)
   p.sk_tk = -1;
-  if (S > 1 && S <= 8 && tiles <= 256 && fits && !(e && e[0] == '0')) {
+  if (S > 1 && S <= 8 && tiles_n <= 256 && fits && !(e && e[0] == '0')) {
     static std::atomic<unsigned> next{0};
     p.sk_tk = (int)((next.fetch_add(1) % (SK_CTRS / 256)) * 256);
   }
-  hipLaunchKernelGGL((gemm_skinny64_kernel<W, NC, MB, F8W>), dim3((unsigned)tiles_n, (unsigned)((p.M + 63) / 64), S),
-                     dim3(W * 64), 0, st, p);
+  hipLaunchKernelGGL((gemm_skinny64_kernel<W, 16, MB, F8W>), dim3((unsigned)tiles_n, 1, S), dim3(W * 64), 0, st, p);
   PZ_CHECK_LAUNCH();
   if (S > 1 && p.sk_tk < 0) return pz_splitk_epi_launch(p, S, st);
   return PZ_OK;
 }
 
-template <int W, int MB, bool F8W>
-static int launch_sk64_nc(const GemmP& p, int nc, int64_t tiles_n, hipStream_t st) {
-  if (nc == 4) return launch_sk64<W, 4, MB, F8W>(p, tiles_n, st);
-  if (nc == 8) return launch_sk64<W, 8, MB, F8W>(p, tiles_n, st);
-  return launch_sk64<W, 16, MB, F8W>(p, tiles_n, st);
-}
-
 template <bool F8W>
-static int launch_sk64_any(const GemmP& p, int w, int nc, int mb, int64_t tn, hipStream_t st) {
+static int launch_sk64_any(const GemmP& p, int w, int mb, int64_t tn, hipStream_t st) {
   if (w == 8) {
-    if (mb == 1) return launch_sk64_nc<8, 1, F8W>(p, nc, tn, st);
-    if (mb == 2) return launch_sk64_nc<8, 2, F8W>(p, nc, tn, st);
-    return launch_sk64_nc<8, 4, F8W>(p, nc, tn, st);
+    if (mb == 1) return launch_sk64<8, 1, F8W>(p, tn, st);
+    if (mb == 2) return launch_sk64<8, 2, F8W>(p, tn, st);
+    return launch_sk64<8, 4, F8W>(p, tn, st);
   }
-  if (mb == 1) return launch_sk64_nc<4, 1, F8W>(p, nc, tn, st);
-  if (mb == 2) return launch_sk64_nc<4, 2, F8W>(p, nc, tn, st);
-  return launch_sk64_nc<4, 4, F8W>(p, nc, tn, st);
+  if (mb == 1) return launch_sk64<4, 1, F8W>(p, tn, st);
+  if (mb == 2) return launch_sk64<4, 2, F8W>(p, tn, st);
+  return launch_sk64<4, 4, F8W>(p, tn, st);
 }
 
-int pz_sk64_launch(const GemmP& p, int w, int nc, int mb, bool f8w, int64_t tiles_n, hipStream_t st) {
-  return f8w ? launch_sk64_any<true>(p, w, nc, mb, tiles_n, st) : launch_sk64_any<false>(p, w, nc, mb, tiles_n, st);
+int pz_sk64_launch(const GemmP& p, int w, int mb, bool f8w, int64_t tiles_n, hipStream_t st) {
+  return f8w ? launch_sk64_any<true>(p, w, mb, tiles_n, st) : launch_sk64_any<false>(p, w, mb, tiles_n, st);
 }

@@ -34,7 +34,7 @@ from dataclasses import dataclass
 import torch
 
 from . import ops
-from .ops import PZ_EPI_DGEGLU, PZ_EPI_DGELU, PZ_EPI_GEGLU, PZ_EPI_GELU, PZ_EPI_NONE, PZ_EPI_SILU
+from .ops import PZ_EPI_DGEGLU, PZ_EPI_GEGLU, PZ_EPI_GELU, PZ_EPI_NONE, PZ_EPI_SILU
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -344,52 +344,40 @@ class Engine:
         # joint attention kernel: "gemm" = MFMA GEMMs around the soft-cap/block-mask softmax, "flash" = the
         # fused pz_flash kernels fwd + bwd (no L x L tensors), "probs" = fused forward that exports the
         # bf16 softmax (pz_flash_fwd_probs: no fp32 S, no softmax launch) + the GEMM-path backward
-        # (default "probs": measured 237.5 vs 235.4 samples/s for "gemm" and 227.5 vs 231.1 for "flash")
-        ja = os.environ.get("PZ_JOINT_ATTN", "probs")
-        self.joint_flash = ja == "flash"
-        self.joint_probs = ja == "probs"
-        # GEMM-path backward's dS: "1" (default) = pz_flash_bwd_ds from the exported P (no fp32 dP), "0" = the
-        # dP GEMM + pz_attn_softmax_bwd (A/B)
-        self.joint_ds = os.environ.get("PZ_JOINT_DS", "1") == "1"
-        # ... and dQ = dS K inside that launch ("0": the batched dQ GEMM, A/B)
-        self.joint_ds_dq = os.environ.get("PZ_JOINT_DS_DQ", "1") == "1"
-        # inference (prefill / denoise) attention: fused kernel unless PZ_INFER_ATTN=gemm
-        self.infer_flash = os.environ.get("PZ_INFER_ATTN", "flash") == "flash"
-        # activation backward of the training MLPs (PZ_SPLIT_DACT, A/B): "1" (default) = plain dgrad GEMM + a
-        # vectorised elementwise pass; "0" = fused into the dgrad GEMM's epilogue, which the 8-phase kernel
-        # cannot overlap with its main loop (measured: "1" +0.7 % samples/s)
-        self.split_dact = os.environ.get("PZ_SPLIT_DACT", "1") == "1"
-        # ... and of the Gemma GeGLU MLPs (PZ_SPLIT_DGEGLU, A/B): "0" (default) = d(gate|up) in the down-proj dgrad
-        # epilogue, which became the faster form once the activations ran on the hardware exp / rcp (vlm layer
-        # 1.390 vs 1.553 ms, action 24.2 vs 26.0 us, tools/dact_ab.py, profiles/r03/dact_ab.log); "1" = plain dgrad
-        # + the separate geglu_bwd pass
-        self.split_dgeglu = os.environ.get("PZ_SPLIT_DGEGLU", "0") == "1"
+        # ("probs": measured 237.5 vs 235.4 samples/s for "gemm" and 227.5 vs 231.1 for "flash").  The GEMM-path
+        # backward takes dS and dQ = dS K from pz_flash_bwd_ds (the exported P, no fp32 dP) where its shape allows.
+        self.joint_flash = False
+        self.joint_probs = True
+        # inference (prefill / denoise) attention: the fused kernel (False: the GEMM path)
+        self.infer_flash = True
+        # Activation backward of the training MLPs.  SigLIP: plain dgrad GEMM + a vectorised elementwise GELU pass
+        # (fused into the dgrad epilogue, which the 8-phase kernel cannot overlap with its main loop, measured 0.7 %
+        # fewer samples/s).  Gemma GeGLU: d(gate|up) in the down-proj dgrad epilogue, the faster form since the
+        # activations run on the hardware exp / rcp (vlm layer 1.390 vs 1.553 ms, action 24.2 vs 26.0 us with the
+        # separate geglu_bwd pass, profiles/r03/dact_ab.log).
         # q|k|v GEMM with the RoPE + Q/K/V scatter in its epilogue (pz_gemm_qkv_rope) where the 8-phase kernel
-        # runs; PZ_FUSE_QKV_ROPE=0: GEMM + pz_qkv_rope_split (A/B, bit-identical)
-        self.fuse_qkv_rope = os.environ.get("PZ_FUSE_QKV_ROPE", "1") == "1" and self.d.hd == 256
+        # runs, bit-identical to GEMM + pz_qkv_rope_split (which other shapes fall back to)
+        self.fuse_qkv_rope = self.d.hd == 256
         # backward of the action-expert group (M = B*(C+H) = 320 rows: latency-bound GEMMs) on a second HIP
-        # stream, concurrent with the vlm group's (PZ_EXPERT_STREAM=0: one stream, A/B)
-        self.expert_stream = os.environ.get("PZ_EXPERT_STREAM", "1") == "1"
-        # ... and in the forward (PZ_EXPERT_STREAM_FWD=1): measured no faster than backward-only (bench 238.9 vs
-        # 239.3 samples/s), and its expert GEMMs then share the CUs with the vlm GeGLU GEMM (the dominant
-        # kernel: live roofline 2.32 vs 2.19 ms per launch), so off by default
-        self.expert_stream_fwd = os.environ.get("PZ_EXPERT_STREAM_FWD", "0") == "1"
+        # stream, concurrent with the vlm group's (False: one stream)
+        self.expert_stream = True
+        # ... and in the forward: measured no faster than backward-only (bench 238.9 vs 239.3 samples/s), and its
+        # expert GEMMs then share the CUs with the vlm GeGLU GEMM (the dominant kernel: live roofline 2.32 vs
+        # 2.19 ms per launch), so off
+        self.expert_stream_fwd = False
         # row pitch of SigLIP's MLP activations (fc1 output / pre-activation / their gradient, 4304 wide): rounded up
         # to 64 elements, so every row starts on a 128-B line (8704 B instead of 8608 B).  The GEMMs that stream
         # these rows run 2-8 % faster with bitwise-equal results (profiles/r04/ld_pad_ab.txt); the pad columns are
-        # never read (K tails clamp their sources into the row).  PZ_SIG_PITCH=0: natural pitch (A/B)
-        vI = self.d.vI
-        self.sig_pitch = vI if os.environ.get("PZ_SIG_PITCH", "1") == "0" else (vI + 63) // 64 * 64
+        # never read (K tails clamp their sources into the row).
+        self.sig_pitch = (self.d.vI + 63) // 64 * 64
         self._side = {}
         # PZ_CHECK_FINITE=1 (debug): after every layer / stage of the training forward and backward (and in
         # FusedAdamW.step) synchronise and check the stage's outputs; the first non-finite tensor raises
         # FloatingPointError naming the stage, the tensor and the kernels launched since the previous check
         self.check_finite = os.environ.get("PZ_CHECK_FINITE", "0") == "1"
         # fp8 inference (C5): weight key -> (e4m3 codes, per-tensor scale); built by prepare_fp8()
-        # in fp8 mode the prefill's joint attention runs S = Q K^T and P V on the fp8 MFMA (pz_flash_fwd_f8;
-        # PZ_FP8_ATTN=0: the bf16 kernel, A/B) and the 65..1024-row q|k|v / o projections run W8A8 on the row-slab
-        # kernel (activation rows quantised per row; PZ_ROWS_W8A8=0: W8A16 as in round 5)
-        self.f8_attn = os.environ.get("PZ_FP8_ATTN", "1") == "1"
+        # in fp8 mode the prefill's joint attention runs S = Q K^T and P V on the fp8 MFMA (pz_flash_fwd_f8) and the
+        # 65..1024-row q|k|v / o projections run W8A8 on the row-slab kernel (activation rows quantised per row)
         self.f8 = None
         self.f8_version = None
         # LoRA (lora: True): adapter sites of the training path, and the merged shadow the inference paths read
@@ -558,9 +546,8 @@ class Engine:
     def w8a8_in(self, key, M, K):
         """fp8 mode: True if the Linear ``key`` on M > 64 rows should get its A operand as e4m3 codes from a fused norm
         (pz_rmsnorm_fwd_f8 / pz_layernorm_fwd_f8): W8A8 on the fp8 MFMA (row slab or 8-phase) with no quantisation
-        launch (PZ_FUSED_NORM_F8=0: bf16 norm output, lin() quantises or runs W8A16)"""
-        return (self.f8 is not None and key in self.f8 and M > 64 and K % 16 == 0 and
-                os.environ.get("PZ_FUSED_NORM_F8", "1") != "0")
+        launch"""
+        return self.f8 is not None and key in self.f8 and M > 64 and K % 16 == 0
 
     def norm_codes(self, x, w, eps, b=None):
         """(codes [M, K], row scales [M]) of RMSNorm (b None) / LayerNorm (b given) of x, in one launch"""
@@ -769,16 +756,16 @@ class Engine:
         pw = torch.empty(P, d.vH, device=dev, dtype=F32)
         pb = torch.empty(P, d.vH, device=dev, dtype=F32)
         # bias gradients fused into the passes that produce their output gradients (LayerNorm backward -> the
-        # column sums of dx: fc2 / out_proj; GELU backward -> fc1); PZ_FUSED_BIAS_GRAD=0: separate colsum passes
-        fb = os.environ.get("PZ_FUSED_BIAS_GRAD", "1") != "0" and os.environ.get("PZ_NORM_BWD", "row")[:1] != "w"
+        # column sums of dx: fc2 / out_proj; GELU backward -> fc1); separate colsum passes under PZ_NORM_BWD=wave,
+        # whose LayerNorm backward yields no partials
+        fb = os.environ.get("PZ_NORM_BWD", "row")[:1] != "w"
         pd = torch.empty(P, d.vH, device=dev, dtype=F32) if fb else None  # column partials of the current dx
         pdn = torch.empty(P, d.vH, device=dev, dtype=F32) if fb else None  # ... of the next layer's dx
         pd2 = torch.empty(P, d.vH, device=dev, dtype=F32) if fb else None  # ... of dxm
         # a layer's LayerNorm weight / bias and Linear bias reductions go out as one launch at its end
-        # (pz_reduce_parts_multi; PZ_REDUCE_MULTI=0: one launch each)
-        multi = os.environ.get("PZ_REDUCE_MULTI", "1") != "0"
-        pw2 = torch.empty(P, d.vH, device=dev, dtype=F32) if multi else pw
-        pb2 = torch.empty(P, d.vH, device=dev, dtype=F32) if multi else pb
+        # (pz_reduce_parts_multi), so its two LayerNorms keep their own partials
+        pw2 = torch.empty(P, d.vH, device=dev, dtype=F32)
+        pb2 = torch.empty(P, d.vH, device=dev, dtype=F32)
         ws_act = self.colsum_ws_rows(1024, d.vI) if fb else None
         # projector
         nm = "multi_modal_projector.linear."
@@ -809,7 +796,7 @@ class Engine:
         for i in reversed(range(d.vL)):
             p = f"{vt}encoder.layers.{i}."
             st = sv["layers"][i]
-            red = [] if multi else None  # deferred (partials, gradient) reductions of this layer
+            red = []  # deferred (partials, gradient) reductions of this layer
             # MLP: x' = xm + fc2(gelu(fc1(ln2(xm))))
             # dgrad through fc2, then the GELU derivative at the saved pre-activation a1
             fc1b = self.rg(p + "mlp.fc1.bias")
@@ -820,14 +807,12 @@ class Engine:
             if s_fc2 is not None:
                 lo = s_fc2.bwd(dx)
                 s_fc2.grads(st["g1"], st["u_fc2"], dx, lo[0], beta)
-            if self.split_dact:  # plain dgrad GEMM, then the GELU backward (HBM-bound) in place
-                ops.linear_dgrad(dx, self.w(p + "mlp.fc2.weight"), dg, lora=lo)
-                if fb and fc1b:  # + the fc1 bias gradient from the same pass
-                    ops.act_bwd_colsum(dg, st["a1"], dg, PZ_EPI_GELU, ws_act, self.gw(p + "mlp.fc1.bias"), beta=beta)
-                else:
-                    ops.act_bwd(dg, st["a1"], dg, None, PZ_EPI_GELU)
+            # plain dgrad GEMM, then the GELU backward (HBM-bound) in place
+            ops.linear_dgrad(dx, self.w(p + "mlp.fc2.weight"), dg, lora=lo)
+            if fb and fc1b:  # + the fc1 bias gradient from the same pass
+                ops.act_bwd_colsum(dg, st["a1"], dg, PZ_EPI_GELU, ws_act, self.gw(p + "mlp.fc1.bias"), beta=beta)
             else:
-                ops.linear_dgrad(dx, self.w(p + "mlp.fc2.weight"), dg, epi=PZ_EPI_DGELU, aux=st["a1"], lora=lo)
+                ops.act_bwd(dg, st["a1"], dg, None, PZ_EPI_GELU)
             if self.rg(p + "mlp.fc2.weight"):
                 ops.linear_wgrad(dx, st["g1"], self.gw(p + "mlp.fc2.weight"), beta=beta)
             st["g1"] = None
@@ -838,7 +823,7 @@ class Engine:
                     ops.colsum(dx, self.gw(p + "mlp.fc2.bias"), ws, beta=beta)
             if self.rg(p + "mlp.fc1.weight"):
                 ops.linear_wgrad(dg, st["h2"], self.gw(p + "mlp.fc1.weight"), beta=beta)
-            if fc1b and not (fb and self.split_dact):
+            if fc1b and not fb:
                 ops.colsum(dg, self.gw(p + "mlp.fc1.bias"), ws, beta=beta)
             lo = None
             if s_fc1 is not None:
@@ -1254,13 +1239,7 @@ class Engine:
         if s_dn is not None:
             lo = s_dn.bwd(dx)
             s_dn.grads(gs["hm"], gs["u_dn"], dx, lo[0], beta)
-        if self.split_dgeglu:  # plain dgrad GEMM, then the HBM-bound GeGLU backward in place on gu
-            dh = torch.empty(M, g.inter, device=dev, dtype=BF16)
-            ops.linear_dgrad(dx, self.w(p + "mlp.down_proj.weight"), dh, lora=lo)
-            ops.geglu_bwd(dh, gu, gu, None, M, g.inter)
-            del dh
-        else:
-            ops.linear_dgrad(dx, self.w(p + "mlp.down_proj.weight"), gu, epi=PZ_EPI_DGEGLU, aux=gu, lora=lo)
+        ops.linear_dgrad(dx, self.w(p + "mlp.down_proj.weight"), gu, epi=PZ_EPI_DGEGLU, aux=gu, lora=lo)
         if self.rg(p + "mlp.down_proj.weight"):
             ops.linear_wgrad(dx, gs["hm"], self.gw(p + "mlp.down_proj.weight"), beta=beta)
         gs["hm"] = None
@@ -1407,15 +1386,15 @@ class Engine:
             else:
                 Pm, tc, Qj, Kj, Vj = st["P"], st["tc"], st["Q"], st["K"], st["V"]
                 dq_done = False
-                if self.joint_ds and not isinstance(cnt, GeneralMask) and L <= 320 and hd == 256:
+                if not isinstance(cnt, GeneralMask) and L <= 320 and hd == 256:
                     # dS in one kernel: dP = dO V^T in registers, delta and the soft-cap/softmax backward
                     # from the exported P / tanh(cap) (no fp32 dP tensor), then dQ = dS K in the same launch;
                     # a mixture without dO adds 0
                     if dS is None:
                         dS = torch.empty(B, L * nh, Lp, device=dev, dtype=BF16)
                     ops.flash_bwd_ds(self._joint_flash(groups, Qj, Kj, Vj, st["O"], None, cnt, B, L, dO=dO,
-                                                       dq=dQ if self.joint_ds_dq else None), Pm, tc, dS, Lp)
-                    dq_done = self.joint_ds_dq
+                                                       dq=dQ), Pm, tc, dS, Lp)
+                    dq_done = True
                 else:
                     if dP is None:
                         dP = torch.empty(B, L * nh, Lp, device=dev, dtype=F32)
@@ -1668,10 +1647,10 @@ class Engine:
     def decode_attn_ok(self):
         """pz_decode_attn for the denoise attention (head_dim 256, up to 1024 query rows per sample in 32-row
         tiles: C4's 4 tokens x 8 heads = one tile, C5's 50 x 8 = 13 tiles with 2 key chunks per workgroup --
-        measured 23.5 vs 24.3 ms per C5 chunk against the key-split flash kernel); PZ_DECODE_ATTN=0 uses
+        measured 23.5 vs 24.3 ms per C5 chunk against the key-split flash kernel); other shapes use
         the flash kernel + combine"""
         d = self.d
-        return d.hd == 256 and os.environ.get("PZ_DECODE_ATTN", "1") != "0" and d.H * d.nh <= 1024
+        return d.hd == 256 and d.H * d.nh <= 1024
 
     def _qkv_w_f8(self, p):
         """(q|k|v weights, fp8 scale): the e4m3 codes and their scale when prepare_fp8() holds them for layer p,
@@ -1770,7 +1749,7 @@ class Engine:
             if self.infer_flash and not isinstance(cnt, GeneralMask):  # fused attention over the L1 prefix keys
                 Os = {g.name: torch.empty(B * g.T, nh * hd, device=dev, dtype=BF16) for g in groups}
                 fa = self._attn_flash_infer(Q, Kj, Vj, [(g.off, g.T, Os[g.name]) for g in groups], L1, L1, 0, cnt, B)
-                if self.f8 is not None and self.f8_attn and hd == 256:
+                if self.f8 is not None and hd == 256:
                     self._flash_f8(fa, Q, Kj, Vj, B, L1 * nh, L1)  # fp8 MFMA attention (C5, configs[4])
                 else:
                     ops.flash_fwd(fa)
@@ -1935,7 +1914,7 @@ class Engine:
             ops.action_in(action, self.w("action_encoder.linear_1.weight"), self.w("action_encoder.linear_1.bias"), t,
                           cat, B, d.H, d.aH, d.tmax, ref_bf16=d.time_bf16)
             sq = math.sqrt(d.aH)
-            if sq.is_integer() and (int(sq) & (int(sq) - 1)) == 0 and os.environ.get("PZ_FOLD_SCALE", "1") != "0":
+            if sq.is_integer() and (int(sq) & (int(sq) - 1)) == 0:
                 # the joint model's sqrt(hidden) input scaling is a power of two (32 at hidden 1024): folded into the
                 # last encoder Linear as alpha with a pre-scaled bias -- 2^k (acc + b) rounds exactly like rounding
                 # first and scaling the bf16 after (the copy_rows launch it replaces), so the bits are unchanged

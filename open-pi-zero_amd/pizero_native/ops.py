@@ -247,25 +247,16 @@ def linear_fp8(x, Wq, w_scale, out, *, bias=None, resid=None, epi=PZ_EPI_NONE, a
     return out
 
 
-def rows_w8a8_ok(M, K, ncols, epi=PZ_EPI_NONE):
-    """both operands e4m3 above 64 rows on the W8A8 row-slab kernel (pz_gemm.hip make_plan: 64 < M <= 1024, K % 128
-    == 0, K <= 2048, <= 4096 output columns, no GeGLU; PZ_ROWS_W8A8=0 disables: W8A16 as before)"""
-    import os
-
-    if os.environ.get("PZ_ROWS_W8A8") == "0":
-        return False
-    return 64 < M <= 1024 and K % 128 == 0 and K <= 2048 and ncols <= 4096 and epi != PZ_EPI_GEGLU
-
-
 def rows_w8a16_ok(M, K, ncols):
     """e4m3 weights with bf16 rows above 64 rows: the row-slab kernel's shapes (pz_gemm.hip plan_rows: 64 < M <=
-    PZ_ROWS_MAXM (1024), K % 64 == 0, K <= 2048, <= 4096 output columns; PZ_GEMM_ROWS=0 disables)"""
+    1024, K % 64 == 0, K <= 2048, <= 4096 output columns; PZ_GEMM_ROWS=0: never, =1: any K / width, as the planner).
+    tests/test_abi.py::test_gemm_routes_golden holds this to the planner."""
     import os
 
-    if os.environ.get("PZ_GEMM_ROWS") == "0" or os.environ.get("PZ_ROWS_W8A16") == "0":
+    rows = os.environ.get("PZ_GEMM_ROWS")
+    if rows == "0":
         return False
-    maxm = int(os.environ.get("PZ_ROWS_MAXM", "1024"))
-    return 64 < M <= maxm and K % 64 == 0 and (os.environ.get("PZ_GEMM_ROWS") == "1" or (K <= 2048 and ncols <= 4096))
+    return 64 < M <= 1024 and K % 64 == 0 and (rows == "1" or (K <= 2048 and ncols <= 4096))
 
 
 def linear_dgrad(dy, W, dx, *, beta=False, resid=None, epi=PZ_EPI_NONE, aux=None, lora=None):

@@ -73,3 +73,62 @@ def test_gemm_planner_routes_without_gpu():
     assert ops.gemm_kernel_name(1280, 2560, 1024).startswith("gemm_kernel<")
     assert ops.gemm_kernel_name(8192, 1024, 1280, a_kc=False, b_kc=False).startswith("gemm_kernel<")
     assert ops.gemm_kernel_name(1280, 1024, 8192, b_kc=False).startswith("gemm8k_kernel")  # K 8192: 256 + tail
+
+
+def _load_make_gemm_routes():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("make_gemm_routes",
+                                                  os.path.join(ROOT, "tests", "golden", "make_gemm_routes.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_gemm_routes_golden(monkeypatch):
+    """The planner's whole routing table (tests/golden/gemm_routes.json, written by make_gemm_routes.py from the
+    library as it stood before the concluded A/B knobs were retired) with no PZ_* variable set: every kernel name,
+    tile count and split count of ~75,000 argument sets is unchanged.  ops.rows_w8a16_ok, the Python mirror of
+    plan_rows that decides whether activations above 64 rows stay bf16, agrees with the planner on every W8A16
+    query above 64 rows."""
+    import json
+
+    from pizero_native import ops
+
+    for k in [k for k in os.environ if k.startswith("PZ_")]:
+        monkeypatch.delenv(k)
+    mk = _load_make_gemm_routes()
+    fx = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_routes.json")))
+    want = mk.decode(fx)
+    qs = list(mk.queries(fx["axes"]))
+    assert len(qs) == len(want) == fx["queries"]
+    bad, mirror = [], []
+    for (M, N, K, kw), w in zip(qs, want):
+        got = ops.gemm_kernel_name(M, N, K, **kw)
+        if got != w:
+            bad.append((M, N, K, kw, got, w))
+        if kw["fp8_mode"] == 2 and M > 64 and K % 64 == 0:
+            ncols = kw["geglu_inter"] if kw["epi"] == ops.PZ_EPI_GEGLU else N
+            if ops.rows_w8a16_ok(M, K, ncols) != got.startswith("gemm_rows_kernel"):
+                mirror.append((M, N, K, kw, got))
+    assert not bad, f"{len(bad)} of {len(qs)} routes changed, first: {bad[:5]}"
+    assert not mirror, f"ops.rows_w8a16_ok disagrees with the planner on {len(mirror)} shapes, first: {mirror[:5]}"
+
+
+def test_env_knob_census():
+    """Every PZ_* environment variable that the library (getenv) or the Python package (os.environ) reads is a row
+    of DESIGN.md's "Environment variables" table, and the table lists no variable that nothing reads."""
+    read = set()
+    pkg = os.path.join(ROOT, "open-pi-zero_amd")
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            if not f.endswith((".hip", ".h", ".py")):
+                continue
+            src = open(os.path.join(d, f)).read()
+            read |= set(re.findall(r'getenv\(\s*"(PZ_[A-Z0-9_]+)"', src))
+            read |= set(re.findall(r'os\.environ(?:\.get\(|\.setdefault\(|\.pop\(|\[)\s*"(PZ_[A-Z0-9_]+)"', src))
+    doc = open(os.path.join(ROOT, "DESIGN.md")).read()
+    sec = doc.split("### Environment variables", 1)[1].split("\n## ", 1)[0]
+    table = set(re.findall(r"^\| `(PZ_[A-Z0-9_]+)` \|", sec, flags=re.M))
+    assert len(read) >= 10, read
+    assert read == table, f"read but not in DESIGN.md: {sorted(read - table)}; listed but never read: {sorted(table - read)}"

@@ -1010,8 +1010,8 @@ def test_gemm_qkv_rope_bit_identical_to_gemm_plus_split(B, T, off):
 def test_gemm_tall_forward_epilogues(M, N, K, monkeypatch):
     """Tall-tile GEMM (pz_gemm_tall.hip, PZ_GEMM_TALL=1: one 256- / 320-row tile over 64 < M <= 1024 rows, K split
     over blockIdx.y + fixed-order split-K sum): bias + residual, GELU + saved pre-activation and fp32 beta
-    accumulation against torch fp32; K tails (K % 64 != 0), ragged rows / columns.  (The GeGLU and k-strided-B
-    forms are built only with -DPZ_TALL_AB: the planner never takes them.)"""
+    accumulation against torch fp32; K tails (K % 64 != 0), ragged rows / columns.  (GeGLU and a k-strided B
+    never take this kernel.)"""
     from pizero_native import ops
 
     monkeypatch.setenv("PZ_GEMM_TALL", "1")

@@ -1,5 +1,5 @@
 """GeGLU backward of the Gemma MLP: down-proj dgrad with the derivative in its epilogue (PZ_EPI_DGEGLU) vs a
-plain dgrad + the separate HBM-bound geglu_bwd pass (engine PZ_SPLIT_DACT=1, the default).  Measurement tool.
+plain dgrad + the separate HBM-bound geglu_bwd pass (the engine runs the fused form).  Measurement tool.
 
     python tools/dact_ab.py [--iters 20]
 """

@@ -6,7 +6,7 @@ siglip: B x 16 heads x 256 x 256, head 72.  Prints fwd / bwd ms and TF/s (algori
 FLOP: fwd 4*nq*nk*hd per unit, bwd 2.5x fwd).
 
 Non-default variants timed beside the defaults: the all-fused joint kernels (pz_flash_fwd / pz_flash_bwd, the
-PZ_JOINT_ATTN=flash path) and the one-workgroup-per-unit / resident SigLIP kernels (PZ_FLASH_SIG=0, PZ_FLASH_UNIT=0).
+Engine.joint_flash path) and the one-workgroup-per-unit / resident SigLIP kernels (PZ_FLASH_SIG=0, PZ_FLASH_UNIT=0).
 (The round-4 register-staged joint kernels, the separate SigLIP delta pass and the 8 x 32-row SigLIP forward were
 measured slower and removed in round 6: profiles/r05/flash_bench_r5l.log.)
 """
@@ -71,7 +71,7 @@ def main():
     tp, td = sorted(tps)[len(tps) // 2], sorted(tds)[len(tds) // 2]
     print(f"joint(dma=1)  fwd+probs {tp:.3f} ms {fl / tp / 1e9:.0f} TF/s (O + bf16 P / tanh(cap) export)   "
           f"bwd dS {td:.3f} ms (+ dQ)  (median of {len(tps)} rounds)", flush=True)
-    if not a.default_only:  # the all-fused joint kernels (PZ_JOINT_ATTN=flash)
+    if not a.default_only:  # the all-fused joint kernels (Engine.joint_flash)
         tf = timeit(lambda: ops.flash_fwd(fa), a.iters)
         tb = timeit(lambda: ops.flash_bwd(fa), a.iters)
         print(f"joint(fused)  fwd {tf:.3f} ms {fl / tf / 1e9:.0f} TF/s   bwd {tb:.3f} ms "

@@ -1,6 +1,6 @@
 """Run one pz_gemm shape/layout a few times (for rocprofv3 counter passes).
 
-    python tools/gemm_one.py --layout TN --M 17664 --N 2048 --K 2048 [--variant 8phase|2stage] [--iters 5]
+    python tools/gemm_one.py --layout TN --M 17664 --N 2048 --K 2048 [--iters 5]
 M, N, K = the forward nn.Linear shape; layouts NT (fwd), NN (dgrad), TN (wgrad) as in tools/gemm_bench.py;
 GEGLU = the vlm gate|up GEMM with the GeGLU epilogue and saved g|u (N = 2 * intermediate); DGEGLU = the down-proj
 dgrad with the GeGLU derivative (M x N x K = tokens x hidden x intermediate, e.g. --M 70656 --N 2048 --K 16384).
@@ -23,11 +23,9 @@ def main():
     ap.add_argument("--M", type=int, default=17664)
     ap.add_argument("--N", type=int, default=2048)
     ap.add_argument("--K", type=int, default=2048)
-    ap.add_argument("--variant", default="8phase")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--notail", action="store_true", help="PZ_GEMM_TAIL=0: whole tiles only")
     a = ap.parse_args()
-    os.environ["PZ_GEMM_BIG"] = a.variant
     if a.notail:
         os.environ["PZ_GEMM_TAIL"] = "0"
     from pizero_native import ops
@@ -57,7 +55,7 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / a.iters
-    print(f"{a.layout} {a.variant} M={M} N={N} K={K}: {ms:.3f} ms {2.0 * M * N * K / ms / 1e9:.1f} TF/s", flush=True)
+    print(f"{a.layout} M={M} N={N} K={K}: {ms:.3f} ms {2.0 * M * N * K / ms / 1e9:.1f} TF/s", flush=True)
 
 
 if __name__ == "__main__":

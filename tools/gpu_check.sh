@@ -61,8 +61,9 @@ PY
         > "$OUT/ab_mb256.log" 2>&1
       timeout -k 10 500 python -u bench.py --steps ${AB_STEPS:-3} --warmup 1 --no-infer --no-cpu-baseline \
         --micro-batch 128 > "$OUT/ab_mb128.log" 2>&1 ;;
-    knobab)  # engine knobs at the default micro-batch, same box: one bench line each (--no-infer)
-      for kv in ${KNOBS:-base PZ_SPLIT_DGEGLU=1 PZ_SPLIT_DACT=0 PZ_EXPERT_STREAM=0 PZ_JOINT_ATTN=gemm base}; do
+    knobab)  # environment knobs (KNOBS: "base" = defaults, or VAR=value each) at the default micro-batch, same box:
+             # one bench line each (--no-infer)
+      for kv in ${KNOBS:-base PZ_NORM_BWD=wave PZ_GEMM_TAIL=0 base}; do
         if [ "$kv" = base ]; then envs=(); else envs=("$kv"); fi
         env "${envs[@]}" timeout -k 10 400 python -u bench.py --steps 3 --warmup 1 --no-infer --no-cpu-baseline \
           > "$OUT/knob.tmp" 2>&1
@@ -108,8 +109,6 @@ PY
         --timeout-method thread > "$OUT/launcher.log" 2>&1 ;;
     normbench)  # memory-bound backward kernels (norms, GELU backward + column sums) under their A/B knobs
       timeout -k 10 300 python -u tools/norm_bench.py > "$OUT/norm_bench.log" 2>&1 ;;
-    attngemm)  # planner A/B on the joint attention's batched dK / dV and the action expert's 1280-row GEMMs
-      timeout -k 10 300 python -u tools/attn_gemm_ab.py > "$OUT/attn_gemm_ab.log" 2>&1 ;;
     infab)  # inference knobs on the C4 / C5 graphs, interleaved (KNOBS: "base" = defaults, or VAR=value each)
       for kv in ${KNOBS:-base base}; do
         if [ "$kv" = base ]; then envs=(); else envs=("$kv"); fi
