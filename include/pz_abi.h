@@ -500,6 +500,41 @@ int pz_lora_wgrad(const void* Q, int64_t ldq, const void* P, int64_t ldp, void* 
 int pz_avg_lerp(void* avg, const void* p, int64_t n, float w, void* stream);
 int pz_avg_swap(void* a, void* b, int64_t n, void* stream);
 
+/* Observation front end / action back end of the inference path (csrc/pz_obs.hip): the reference's env
+ * adapter (src/agent/env_adapter/base.py:8-49, simpler.py:53-126) and its data pipeline's resize (dlimp/utils.py:12-17)
+ * as kernels that run inside the captured inference graph.  Entry points added under ABI 22 (no existing signature
+ * changed).
+ *
+ * pz_image_resize_norm: uint8 frames [n, H_in, W_in, 3] (channels_last = 1) or [n, 3, H_in, W_in] (0) -> bf16
+ *   out [n, 3, S, S], the buffer pz_patchify reads.  tf.image.resize(method="lanczos3", antialias=True) done
+ *   separably from host-built tap tables, one per axis (h_*: W_in -> S, v_*: H_in -> S), all in device memory:
+ *     *_first int32 [S]: first input index of output i;  *_count int32 [S]: its number of taps (<= *_taps);
+ *     *_w fp32 [S][*_taps]: weights, normalised to sum 1 over the taps (entries past the count are not read).
+ *   Taps whose index falls outside [0, extent) are skipped, so no table content can make the kernel read out of
+ *   bounds.  The horizontal pass writes fp32 into scratch (pz_image_resize_scratch_bytes(n, H_in, S) bytes, 4-byte
+ *   aligned; not rounded to uint8); the vertical pass rounds half-to-even, clips to [0, 255] and stores lut[code],
+ *   lut = 256 bf16 values (the caller's pixel normalisation of each code).  Two launches, no atomics.
+ *   Limits (PZ_ERR_INVALID_ARG before any launch, the message names the limit): h_taps, v_taps <= PZ_OBS_MAX_TAPS
+ *   (a Lanczos-3 window of a downscale up to 10x); H_in, W_in, S <= PZ_OBS_MAX_EXTENT; frames, scratch and out
+ *   pairwise disjoint.
+ * pz_proprio_normalize / pz_action_denormalize: fp32 x [rows, D] -> y [rows, D] (y may be x), statistics a, b fp32 [D]:
+ *   PZ_OBS_NORM_BOUND    (a = lo, b = hi):    y = clip(2 (x - lo) / (hi - lo + 1e-8) - 1, -1, 1);  x = (y + 1) / 2 (hi - lo) + lo
+ *   PZ_OBS_NORM_GAUSSIAN (a = mean, b = std): y = (x - mean) / (std + 1e-8);                       x = y (std + 1e-8) + mean
+ *   evaluated in fp32 as written (no FMA contraction).  pz_action_denormalize copies the trailing n_pass dimensions
+ *   of every row unchanged (the reference leaves the gripper alone, simpler.py:105-126). */
+#define PZ_OBS_MAX_TAPS 64
+#define PZ_OBS_MAX_EXTENT 16384
+enum { PZ_OBS_NORM_BOUND = 0, PZ_OBS_NORM_GAUSSIAN = 1 };
+int64_t pz_image_resize_scratch_bytes(int64_t n, int64_t H_in, int64_t S);
+int pz_image_resize_norm(const void* frames, int32_t channels_last, int64_t n, int64_t H_in, int64_t W_in, int64_t S,
+                         const void* h_first, const void* h_count, const void* h_w, int64_t h_taps,
+                         const void* v_first, const void* v_count, const void* v_w, int64_t v_taps, const void* lut,
+                         void* scratch, int64_t scratch_bytes, void* out, void* stream);
+int pz_proprio_normalize(const void* x, void* y, int64_t rows, int64_t D, const void* a, const void* b, int32_t mode,
+                         void* stream);
+int pz_action_denormalize(const void* x, void* y, int64_t rows, int64_t D, int64_t n_pass, const void* a,
+                          const void* b, int32_t mode, void* stream);
+
 /* test instrument: fill every CU's LDS with `word` (0xffffffff = NaN) on `stream`, so the next kernel's reads of
  * LDS it did not write return NaN (tests/test_train_loop_gpu.py; _lib.call runs it before every launch under
  * PZ_POISON_LDS=1).  Not on any product path. */

@@ -84,3 +84,90 @@ class InferenceGraph:
             self.capture()
         self.graph.replay()
         return self.out
+
+
+class ObservationGraph(InferenceGraph):
+    """The action chunk from RAW observations as one graph replay: uint8 camera frames of any size, raw
+    proprio and token ids in, actions in robot units out.  Captured, in order, on one linear stream:
+
+      1. ``pz_image_resize_norm`` (Lanczos-3 resize + pixel normalisation; its fp32 scratch comes from the graph's
+         pool) and ``pz_proprio_normalize``,
+      2. ``Engine.infer_action``,
+      3. ``pz_action_denormalize`` (the last action dimension, the gripper, passes through).
+
+    The static inputs are the raw ones; the prefix counts are ``attention_mask.sum(1)``, computed by the caller where
+    the mask is born, so no [L, L] mask exists on this path, and the position ids are constants.  ``stats`` is the
+    dataset-statistics dict (``proprio`` / ``action`` -> ``p01``, ``p99``, ``mean``, ``std``) with the optional keys
+    ``proprio_normalization_type`` / ``action_normalization_type`` (``bound`` by default, as in simpler.py:25-26).
+    capture() and replay() are InferenceGraph's: the weight-refresh and re-capture rules are the same.
+    ``run_eager()`` enqueues the same launches without a graph.  ``out`` holds the robot-unit actions and
+    ``out_norm`` the model's normalised chunk they were computed from (both fp32 [B, H, A])."""
+
+    def __init__(self, model, bsz, frame_hw, stats, channels_last=True, clip=True):
+        from . import ops
+
+        self.m = model
+        self.B = bsz
+        self.clip = clip
+        self.channels_last = bool(channels_last)
+        e = model._engine()
+        d = e.d
+        dev = model._dev()
+        h, w = (int(x) for x in frame_hw)
+        ops.lanczos3_taps(h, d.img), ops.lanczos3_taps(w, d.img)  # refuse an unsupported geometry here, not at capture
+        n = bsz * d.n_images
+        self.static = dict(
+            frames=torch.zeros((n, h, w, 3) if self.channels_last else (n, 3, h, w), device=dev, dtype=torch.uint8),
+            ids=torch.zeros(bsz, d.P, device=dev, dtype=torch.int64),
+            cnt=torch.full((bsz,), d.P, device=dev, dtype=torch.int32),
+            vpos=torch.arange(1, d.P + 1, device=dev).repeat(bsz, 1),
+            ppos=torch.arange(1, d.C + 1, device=dev).repeat(bsz, 1),
+            apos=torch.arange(d.C + 1, d.C + d.H + 1, device=dev).repeat(bsz, 1),
+            raw_proprio=torch.zeros(bsz, d.C, d.Pd, device=dev, dtype=torch.float32),
+            noise=torch.zeros(bsz, d.H, d.A, device=dev, dtype=torch.float32),
+        )
+        self.modes = {}
+        self.stat = {}
+        for key, dim in (("proprio", d.Pd), ("action", d.A)):
+            mode = stats.get(f"{key}_normalization_type", "bound")
+            if mode not in ops.NORM_MODES:
+                raise ValueError(f"{key}_normalization_type must be one of {sorted(ops.NORM_MODES)}, got {mode!r}")
+            names = ("p01", "p99") if mode == "bound" else ("mean", "std")
+            ab = [torch.as_tensor(stats[key][nm], dtype=torch.float64).to(torch.float32).to(dev).contiguous()
+                  for nm in names]
+            if any(t.numel() != dim for t in ab):
+                raise ValueError(f"dataset statistics: {key} has {ab[0].numel()} dimensions, the model {dim}")
+            self.modes[key], self.stat[key] = mode, ab
+        self.k, self.v = model._kv_buffers(bsz)
+        self.graph = None
+        self.out = None
+        self.out_norm = None
+        self._f8 = None
+
+    def _run(self):
+        from . import ops
+
+        s = self.static
+        d = self.m._engine().d
+        pix = ops.image_resize_norm(s["frames"], d.img, channels_last=self.channels_last)
+        proprios = ops.proprio_normalize(s["raw_proprio"], *self.stat["proprio"], self.modes["proprio"])
+        self.out_norm = self.m._engine().infer_action(s["ids"], pix, s["cnt"], s["vpos"], s["ppos"], s["apos"],
+                                                      proprios, s["noise"], self.k, self.v, clip=self.clip)
+        return ops.action_denormalize(self.out_norm, *self.stat["action"], self.modes["action"], n_pass=1)
+
+    def load(self, frames, input_ids, cnt, raw_proprio, noise):
+        s = self.static
+        nb = dict(non_blocking=True)
+        s["frames"].copy_(frames.reshape(s["frames"].shape), **nb)
+        s["ids"].copy_(input_ids, **nb)
+        s["cnt"].copy_(cnt.reshape(s["cnt"].shape), **nb)
+        s["raw_proprio"].copy_(raw_proprio.reshape(s["raw_proprio"].shape), **nb)
+        s["noise"].copy_(noise.reshape(s["noise"].shape), **nb)
+
+    def run_eager(self):
+        """the captured launches, enqueued directly on the current stream (``EvalAgent(use_graph=False)``).  ``out`` /
+        ``out_norm`` then name the eager results, so a graph captured earlier is dropped (re-captured on next use)."""
+        self.graph = None
+        self.m._engine().derived_refresh()
+        self.out = self._run()
+        return self.out

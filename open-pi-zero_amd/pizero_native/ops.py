@@ -19,6 +19,10 @@ from ._lib import (
     PZ_EPI_GELU,
     PZ_EPI_NONE,
     PZ_EPI_SILU,
+    PZ_OBS_MAX_EXTENT,
+    PZ_OBS_MAX_TAPS,
+    PZ_OBS_NORM_BOUND,
+    PZ_OBS_NORM_GAUSSIAN,
     PZ_SUMSQ_PARTS,
     AdamW8Args,
     QkvRopeArgs,
@@ -813,6 +817,131 @@ def avg_swap(a, b):
     assert a.dtype == BF16 and b.dtype == BF16 and a.numel() == b.numel()
     assert a.is_contiguous() and b.is_contiguous()
     call("pz_avg_swap", _p(a), _p(b), a.numel(), _st())
+
+
+# ---- observation front end / action back end (csrc/pz_obs.hip) ----------------------------------------
+NORM_MODES = {"bound": PZ_OBS_NORM_BOUND, "gaussian": PZ_OBS_NORM_GAUSSIAN}
+_TAPS = {}  # (n_in, n_out, device) -> (first int32 [n_out], count int32 [n_out], weights fp32 [n_out, T], T)
+_CODE_LUT = {}  # device -> bf16 [256]
+
+
+def lanczos3_taps(n_in, n_out):
+    """Tap table of one axis of tf.image.resize(method="lanczos3", antialias=True), n_in -> n_out, in fp64 numpy:
+    (first int32 [n_out], count int32 [n_out], weights fp64 [n_out, T]).  Output i is centred on c = (i + 0.5) scale
+    (scale = n_in / n_out), the kernel is stretched by ks = max(scale, 1) (the antialias), its taps are the input
+    indices [floor(c - 3 ks + 0.5), floor(c + 3 ks + 0.5)) clipped to [0, n_in), weighted by L3((x + 0.5 - c) / ks),
+    L3(t) = sinc(t) sinc(t / 3) on |t| < 3, and normalised to sum 1.  Columns past an output's count are zero."""
+    import numpy as np
+
+    if int(n_in) != n_in or int(n_out) != n_out or n_in < 1 or n_out < 1:
+        raise ValueError(f"lanczos3_taps: sizes must be positive integers, got {n_in} -> {n_out}")
+    n_in, n_out = int(n_in), int(n_out)
+    if max(n_in, n_out) > PZ_OBS_MAX_EXTENT:
+        raise ValueError(f"lanczos3_taps: {n_in} -> {n_out} exceeds the extent limit PZ_OBS_MAX_EXTENT = "
+                         f"{PZ_OBS_MAX_EXTENT}")
+    scale = n_in / n_out
+    ks = max(scale, 1.0)
+    c = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum(np.floor(c - 3.0 * ks + 0.5), 0).astype(np.int64)
+    hi = np.minimum(np.floor(c + 3.0 * ks + 0.5), n_in).astype(np.int64)
+    count = hi - lo
+    T = int(count.max())
+    if T > PZ_OBS_MAX_TAPS:
+        raise ValueError(f"lanczos3_taps: {n_in} -> {n_out} needs {T} taps per output, above the kernel's limit "
+                         f"PZ_OBS_MAX_TAPS = {PZ_OBS_MAX_TAPS} (a downscale of up to {(PZ_OBS_MAX_TAPS - 2) // 6}x)")
+    x = lo[:, None] + np.arange(T)[None, :]
+    t = (x + 0.5 - c[:, None]) / ks
+    w = np.where((np.abs(t) < 3.0) & (x < hi[:, None]), np.sinc(t) * np.sinc(t / 3.0), 0.0)
+    w = w / w.sum(axis=1, keepdims=True)
+    return lo.astype(np.int32), count.astype(np.int32), w
+
+
+def _device_taps(n_in, n_out, dev):
+    key = (int(n_in), int(n_out), dev)
+    t = _TAPS.get(key)
+    if t is None:
+        first, count, w = lanczos3_taps(n_in, n_out)
+        t = _TAPS[key] = (torch.from_numpy(first).to(dev), torch.from_numpy(count).to(dev),
+                          torch.from_numpy(w).to(torch.float32).contiguous().to(dev), w.shape[1])
+    return t
+
+
+def pixel_code_lut(dev):
+    """bf16 [256]: the model's pixel normalisation of each uint8 code, ((q / 255 - 0.5) / 0.5).to(bf16)
+    (vla/processing.py:109-114), evaluated by torch ON THE HOST and uploaded -- the bits a host-normalised frame
+    carries into EvalAgent.infer_chunk.  (Evaluated on the device the same expression differs in a few codes around
+    127 by one bf16 ulp: there torch divides by a scalar as a multiplication by its reciprocal, and q / 255 - 0.5
+    cancels.)"""
+    dev = torch.device(dev)
+    lut = _CODE_LUT.get(dev)
+    if lut is None:
+        q = torch.arange(256, dtype=torch.int32).to(torch.uint8)
+        lut = _CODE_LUT[dev] = ((q.to(torch.float32) / 255.0 - 0.5) / 0.5).to(BF16).contiguous().to(dev)
+    return lut
+
+
+def image_resize_scratch_numel(n, h_in, S):
+    """fp32 elements of the scratch between the two passes of image_resize_norm"""
+    return lib().pz_image_resize_scratch_bytes(int(n), int(h_in), int(S)) // 4
+
+
+def image_resize_norm(frames, S, channels_last=True, out=None, scratch=None):
+    """uint8 frames [n, H, W, 3] (channels_last) or [n, 3, H, W] -> bf16 [n, 3, S, S]: Lanczos-3 resize with
+    antialiasing (tf.image.resize semantics, lanczos3_taps), rounded half-to-even to a uint8 code and stored in the
+    model's pixel normalisation (pixel_code_lut).  The tap tables and the code table are built on first use of a
+    geometry / device and cached (so: before a graph capture); ``scratch`` (fp32, image_resize_scratch_numel) and
+    ``out`` are allocated from the current allocator when not given."""
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.is_contiguous() and frames.is_cuda
+    n = frames.shape[0]
+    if channels_last:
+        H, W, ch = frames.shape[1:]
+    else:
+        ch, H, W = frames.shape[1:]
+    if ch != 3:
+        raise ValueError(f"image_resize_norm: frames must have 3 channels, got shape {tuple(frames.shape)}")
+    dev = frames.device
+    hf, hc, hw, ht = _device_taps(W, S, dev)
+    vf, vc, vw, vt = _device_taps(H, S, dev)
+    lut = pixel_code_lut(dev)
+    need = image_resize_scratch_numel(n, H, S)
+    if scratch is None:
+        scratch = torch.empty(need, device=dev, dtype=torch.float32)
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= need
+    if out is None:
+        out = torch.empty(n, 3, S, S, device=dev, dtype=BF16)
+    assert out.dtype == BF16 and out.is_contiguous() and tuple(out.shape) == (n, 3, S, S)
+    call("pz_image_resize_norm", _p(frames), int(bool(channels_last)), n, H, W, S, _p(hf), _p(hc), _p(hw), ht,
+         _p(vf), _p(vc), _p(vw), vt, _p(lut), _p(scratch), scratch.numel() * 4, _p(out), _st())
+    return out
+
+
+def _norm_args(x, out, a, b, mode):
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.is_cuda
+    D = x.shape[-1]
+    for s in (a, b):
+        assert s.dtype == torch.float32 and s.is_contiguous() and s.numel() == D and s.device == x.device
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape
+    if mode not in NORM_MODES:
+        raise ValueError(f"normalisation type must be one of {sorted(NORM_MODES)}, got {mode!r}")
+    return out, x.numel() // D, D, NORM_MODES[mode]
+
+
+def proprio_normalize(x, a, b, mode, out=None):
+    """fp32 [..., D] raw proprio -> normalised (env_adapter/base.py): mode "bound" with a = p01, b = p99 gives
+    clip(2 (x - a) / (b - a + 1e-8) - 1, -1, 1); "gaussian" with a = mean, b = std gives (x - a) / (b + 1e-8)."""
+    out, rows, D, m = _norm_args(x, out, a, b, mode)
+    call("pz_proprio_normalize", _p(x), _p(out), rows, D, _p(a), _p(b), m, _st())
+    return out
+
+
+def action_denormalize(x, a, b, mode, n_pass=1, out=None):
+    """fp32 [..., D] normalised actions -> robot units: "bound" (x + 1) / 2 (b - a) + a, "gaussian" x (b + 1e-8) + a;
+    the trailing ``n_pass`` dimensions (the gripper, simpler.py:105-126) are copied unchanged."""
+    out, rows, D, m = _norm_args(x, out, a, b, mode)
+    call("pz_action_denormalize", _p(x), _p(out), rows, D, int(n_pass), _p(a), _p(b), m, _st())
+    return out
 
 
 def debug_poison_lds(word=0xFFFFFFFF):

@@ -5,7 +5,9 @@ Construction mirrors the reference: ``PiZeroInference(cfg)``, checkpoint load
 moves.  The action chunk for one observation is ``infer_chunk`` (mask/position
 building + ``model(**inputs)`` = PiZeroInference.forward, eval.py:99-125); with
 ``use_graph`` the whole chunk replays as one hipGraph (pizero_native/graph.py).
-The SimplerEnv rollout loop and env adapters are out of scope:
+``act`` is the same chunk from RAW observations (camera frames of any size, raw proprio) to actions in robot
+units: the env adapter's resize and normalisation (env_adapter/{base,simpler}.py) run as kernels inside the graph.
+The SimplerEnv rollout loop, the tokenizer and the robot-specific post-processing are out of scope:
 ``run()`` needs ``simpler_env`` and raises without it.
 """
 
@@ -31,6 +33,8 @@ class EvalAgent:
         self.model.eval()
         self.use_graph = use_graph
         self._graphs = {}
+        self._obs_graphs = {}
+        self._stats = None
         self.act_steps = cfg_get(cfg, "act_steps", cfg_get(cfg, "horizon_steps"))
 
     def load_checkpoint(self, path):
@@ -65,6 +69,66 @@ class EvalAgent:
             g.capture()
         g.load(*args)
         return g.replay().to(self.dtype)
+
+    STATS_KEY = "env.adapter.dataset_statistics_path"
+
+    def _dataset_statistics(self):
+        """The env adapter's settings under the reference's names (config/eval/bridge.yaml:19-28, simpler.py:19-37):
+        the statistics JSON and the two normalisation types, as the dict ObservationGraph takes."""
+        if self._stats is None:
+            from src.agent.env_adapter.base import load_dataset_statistics
+
+            path = cfg_get(self.cfg, self.STATS_KEY)
+            if not path:
+                raise ValueError(f"EvalAgent.act needs the dataset statistics: set {self.STATS_KEY} (a JSON file with "
+                                 "proprio / action -> p01, p99, mean, std)")
+            stats = dict(load_dataset_statistics(path))
+            for k in ("proprio_normalization_type", "action_normalization_type"):
+                stats[k] = cfg_get(self.cfg, f"env.adapter.{k}", "bound")
+            self._stats = stats
+        return self._stats
+
+    def observation_graph(self, bsz, frame_hw, channels_last=True):
+        """the ObservationGraph of one (batch size, frame geometry, layout); built on first use, not yet captured"""
+        from pizero_native.graph import ObservationGraph
+
+        key = (bsz, tuple(int(x) for x in frame_hw), bool(channels_last))
+        g = self._obs_graphs.get(key)
+        if g is None:
+            g = self._obs_graphs[key] = ObservationGraph(self.model, bsz, key[1], self._dataset_statistics(),
+                                                         channels_last=channels_last)
+        return g
+
+    @torch.no_grad()
+    def act(self, frames, input_ids, attention_mask, raw_proprio, noise=None, channels_last=True):
+        """Raw observation -> fp32 [B, horizon, action_dim] actions in ROBOT units, one graph replay.
+
+        ``frames``: uint8 camera frames of any size, [B (* n_images), H, W, 3] (or [.., 3, H, W] with
+        ``channels_last=False``), torch or numpy, host or device; ``raw_proprio``: [B, cond_steps, proprio_dim] in
+        robot units; ``input_ids`` / ``attention_mask``: the tokenised prompt.  The Lanczos-3 resize to the model's
+        image size, the pixel and proprio normalisation and the action denormalisation run as HIP kernels inside the
+        captured graph (``use_graph=False``: the same kernels, enqueued eagerly).  The prefix counts are the
+        attention mask's row sums, taken where the mask lives; no [L, L] mask is built.  The returned tensor is the
+        graph's static output: copy it before the next call if it must survive it."""
+        self._dataset_statistics()  # without statistics: the ValueError that names the key, before anything else
+        m = self.model
+        frames, input_ids, attention_mask, raw_proprio = (torch.as_tensor(x) for x in
+                                                          (frames, input_ids, attention_mask, raw_proprio))
+        if frames.dtype != torch.uint8 or frames.dim() != 4:
+            raise ValueError(f"act: frames must be uint8 [n, H, W, 3] or [n, 3, H, W], got {frames.dtype} "
+                             f"{tuple(frames.shape)}")
+        B = input_ids.shape[0]
+        hw = frames.shape[1:3] if channels_last else frames.shape[2:4]
+        cnt = attention_mask.sum(1)
+        if noise is None:
+            noise = torch.randn(B, m.horizon_steps, m.action_dim, device=self.device)
+        g = self.observation_graph(B, hw, channels_last)
+        g.load(frames.contiguous(), input_ids, cnt, raw_proprio.to(torch.float32), noise)
+        if not self.use_graph:
+            return g.run_eager()
+        if g.graph is None:
+            g.capture()
+        return g.replay()
 
     def run(self):
         try:

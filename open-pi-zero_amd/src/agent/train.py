@@ -200,7 +200,14 @@ class TrainAgent:
         am = batch["attention_mask"].to(dev, **nb)
         mask, vpos, ppos, apos = m.build_causal_mask_and_position_ids(am, self.dtype)
         pix = batch["pixel_values"].to(dev, **nb)
-        if pix.dtype == torch.uint8:
+        img = int(cfg_get(self.cfg, "vision.config.image_size"))
+        if pix.dtype == torch.uint8 and pix.dim() == 4 and tuple(pix.shape[-2:]) != (img, img):
+            # frames not yet at the model's resolution: the data pipeline's Lanczos-3 resize (dlimp/utils.py:12-17)
+            # and the pixel normalisation in one native op; [B, 3, H, W] as the dataset delivers them
+            from pizero_native import ops
+
+            pix = ops.image_resize_norm(pix.contiguous(), img, channels_last=False)
+        elif pix.dtype == torch.uint8:
             pix = (pix.to(torch.float32) / 255.0 - 0.5) / 0.5
         inputs = {"input_ids": batch["input_ids"].to(dev, **nb), "pixel_values": pix.to(self.dtype),
                   "vlm_position_ids": vpos, "proprio_position_ids": ppos, "action_position_ids": apos,
