@@ -535,6 +535,44 @@ int pz_proprio_normalize(const void* x, void* y, int64_t rows, int64_t D, const 
 int pz_action_denormalize(const void* x, void* y, int64_t rows, int64_t D, int64_t n_pass, const void* a,
                           const void* b, int32_t mode, void* stream);
 
+/* Training-image augmentation (csrc/pz_augment.hip, pz_image_resize_u8 in csrc/pz_obs.hip): the random
+ * crop and colour jitter of the reference's data pipeline (src/agent/dataset.py:38-70, dlimp/augmentations.py) as
+ * pure functions of host-drawn parameters.  Entry points added under ABI 22 (no existing signature changed).
+ *
+ * pz_image_augment: uint8 frames [n, S, S, 3] (channels_last = 1) or [n, 3, S, S] (0) -> bf16 out [n, 3, S, S], the
+ *   buffer pz_patchify reads.  Per frame f: params fp32 [n][8] = box y1, x1, y2, x2 (fractions of the image, inside
+ *   [0, 1]), brightness delta, contrast factor, saturation factor, hue delta; mask int32 [n] = the PZ_AUG_* ops that
+ *   frame gets (both in device memory).  Fixed order crop, brightness, contrast, saturation, hue on x = q / 255 with
+ *   clip(x, 0, 1) after every op; crop = tf.image.crop_and_resize (bilinear, crop size = image size), contrast about
+ *   the per-channel mean of the frame at that point of the chain, saturation / hue in hexcone HSV; then
+ *   q' = min(floor(255.5 x), 255) and out = lut[q'], lut = 256 bf16 values (the caller's pixel normalisation).
+ *   ops_union is the host's OR over the masks it wants honoured: a frame's effective mask is mask[f] & ops_union,
+ *   and the launch that sums the channel means is skipped when PZ_AUG_CONTRAST is not in it.  scratch (fp32,
+ *   pz_image_augment_scratch_bytes(n, S) bytes, 4-byte aligned) holds the partial sums of the means and may be null
+ *   when ops_union has no contrast.  No atomics, a fixed reduction order that depends on S alone: bitwise
+ *   repeatable, and a frame's output does not depend on the other frames of the call.  Every gather index is
+ *   compared with S before use.  PZ_ERR_INVALID_ARG before any launch (the message names the argument) for null
+ *   pointers, n <= 0 or n > 65535, S <= 0 or S > PZ_OBS_MAX_EXTENT, misaligned params / mask / out / lut / scratch,
+ *   a scratch that is too small, and out or scratch overlapping another buffer.
+ * pz_image_resize_u8: pz_image_resize_norm's two passes (same arguments, same kernels, no lut) storing the rounded
+ *   code as uint8 out [n, 3, S, S] instead of the table value: resize first, augment after, as the reference does. */
+enum {
+  PZ_AUG_CROP = 1,
+  PZ_AUG_BRIGHTNESS = 2,
+  PZ_AUG_CONTRAST = 4,
+  PZ_AUG_SATURATION = 8,
+  PZ_AUG_HUE = 16,
+  PZ_AUG_ALL = 31
+};
+int64_t pz_image_augment_scratch_bytes(int64_t n, int64_t S);
+int pz_image_augment(const void* frames, int32_t channels_last, int64_t n, int64_t S, const void* params,
+                     const void* mask, int32_t ops_union, const void* lut, void* scratch, int64_t scratch_bytes,
+                     void* out, void* stream);
+int pz_image_resize_u8(const void* frames, int32_t channels_last, int64_t n, int64_t H_in, int64_t W_in, int64_t S,
+                       const void* h_first, const void* h_count, const void* h_w, int64_t h_taps, const void* v_first,
+                       const void* v_count, const void* v_w, int64_t v_taps, void* scratch, int64_t scratch_bytes,
+                       void* out, void* stream);
+
 /* test instrument: fill every CU's LDS with `word` (0xffffffff = NaN) on `stream`, so the next kernel's reads of
  * LDS it did not write return NaN (tests/test_train_loop_gpu.py; _lib.call runs it before every launch under
  * PZ_POISON_LDS=1).  Not on any product path. */

@@ -2,6 +2,7 @@
 // env adapter on (src/agent/env_adapter/{base,simpler}.py) and its data pipeline's resize (dlimp/utils.py:12-17).
 //
 //   pz_image_resize_norm   uint8 frames of any size -> bf16 [n, 3, S, S] in the model's pixel normalisation
+//   pz_image_resize_u8     the same two passes, storing the rounded uint8 code (input of pz_image_augment)
 //   pz_proprio_normalize   raw proprio -> the model's normalised proprio (bound | gaussian statistics)
 //   pz_action_denormalize  the model's action chunk -> robot units (trailing dimensions pass through)
 //
@@ -58,8 +59,10 @@ __global__ void __launch_bounds__(OBS_THREADS) resize_h_kernel(const uint8_t* __
   tmp[i] = acc;
 }
 
-// tmp fp32 [n][3][H][S] -> out bf16 [n][3][S][S]
-__global__ void __launch_bounds__(OBS_THREADS) resize_v_kernel(const float* __restrict__ tmp, bf16_t* __restrict__ out,
+// tmp fp32 [n][3][H][S] -> out [n][3][S][S]: OutT = bf16_t stores lut[code], OutT = uint8_t the code itself
+// (pz_image_resize_u8: the frame goes on to pz_image_augment)
+template <typename OutT>
+__global__ void __launch_bounds__(OBS_THREADS) resize_v_kernel(const float* __restrict__ tmp, OutT* __restrict__ out,
                                                                int64_t total, int H, int S, Taps t,
                                                                const bf16_t* __restrict__ lut) {
   const int64_t i = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x;
@@ -79,7 +82,10 @@ __global__ void __launch_bounds__(OBS_THREADS) resize_v_kernel(const float* __re
     if ((unsigned)y < (unsigned)H) acc = __builtin_fmaf(w[k], col[(int64_t)y * S], acc);
   }
   const float q = fminf(fmaxf(__builtin_rintf(acc), 0.f), 255.f);  // half-to-even, then clip; NaN cannot occur
-  out[i] = lut[(int)q];
+  if constexpr (sizeof(OutT) == 1)
+    out[i] = (OutT)q;
+  else
+    out[i] = lut[(int)q];
 }
 
 enum { MODE_BOUND = PZ_OBS_NORM_BOUND, MODE_GAUSSIAN = PZ_OBS_NORM_GAUSSIAN };
@@ -141,35 +147,36 @@ extern "C" int64_t pz_image_resize_scratch_bytes(int64_t n, int64_t H_in, int64_
   return n * 3 * H_in * S * (int64_t)sizeof(float);
 }
 
-extern "C" int pz_image_resize_norm(const void* frames, int32_t channels_last, int64_t n, int64_t H_in, int64_t W_in,
-                                    int64_t S, const void* h_first, const void* h_count, const void* h_w,
-                                    int64_t h_taps, const void* v_first, const void* v_count, const void* v_w,
-                                    int64_t v_taps, const void* lut, void* scratch, int64_t scratch_bytes, void* out,
-                                    void* stream) {
-  PZ_CHECK_ARG(frames && out && scratch && lut, "image_resize_norm: null pointer");
-  PZ_CHECK_ARG(h_first && h_count && h_w && v_first && v_count && v_w, "image_resize_norm: null tap table");
-  PZ_CHECK_ARG(channels_last == 0 || channels_last == 1, "image_resize_norm: channels_last must be 0 or 1");
-  PZ_CHECK_ARG(n > 0 && H_in > 0 && W_in > 0 && S > 0, "image_resize_norm: n, H_in, W_in, S must be positive");
+// both resize entry points: code = false stores lut[code] as bf16 (pz_image_resize_norm), true the uint8 code
+static int resize_launch(const char* who, bool code, const void* frames, int32_t channels_last, int64_t n, int64_t H_in,
+                         int64_t W_in, int64_t S, const void* h_first, const void* h_count, const void* h_w,
+                         int64_t h_taps, const void* v_first, const void* v_count, const void* v_w, int64_t v_taps,
+                         const void* lut, void* scratch, int64_t scratch_bytes, void* out, void* stream) {
+  PZ_CHECK_ARG(frames && out && scratch && (lut || code), "%s: null pointer", who);
+  PZ_CHECK_ARG(h_first && h_count && h_w && v_first && v_count && v_w, "%s: null tap table", who);
+  PZ_CHECK_ARG(channels_last == 0 || channels_last == 1, "%s: channels_last must be 0 or 1", who);
+  PZ_CHECK_ARG(n > 0 && H_in > 0 && W_in > 0 && S > 0, "%s: n, H_in, W_in, S must be positive", who);
   PZ_CHECK_ARG(H_in <= PZ_OBS_MAX_EXTENT && W_in <= PZ_OBS_MAX_EXTENT && S <= PZ_OBS_MAX_EXTENT,
-               "image_resize_norm: H_in, W_in and S are limited to %d", PZ_OBS_MAX_EXTENT);
-  PZ_CHECK_ARG(h_taps > 0 && v_taps > 0, "image_resize_norm: tap counts must be positive");
+               "%s: H_in, W_in and S are limited to %d", who, PZ_OBS_MAX_EXTENT);
+  PZ_CHECK_ARG(h_taps > 0 && v_taps > 0, "%s: tap counts must be positive", who);
   PZ_CHECK_ARG(h_taps <= PZ_OBS_MAX_TAPS && v_taps <= PZ_OBS_MAX_TAPS,
-               "image_resize_norm: %lld x %lld taps per output exceed the limit of %d (PZ_OBS_MAX_TAPS: "
+               "%s: %lld x %lld taps per output exceed the limit of %d (PZ_OBS_MAX_TAPS: "
                "a Lanczos-3 downscale of up to %dx)",
-               (long long)h_taps, (long long)v_taps, PZ_OBS_MAX_TAPS, (PZ_OBS_MAX_TAPS - 2) / 6);
-  PZ_CHECK_ARG(PZ_ALIGNED(scratch, 4) && PZ_ALIGNED(out, 2) && PZ_ALIGNED(lut, 2) && PZ_ALIGNED(h_w, 4) &&
-                   PZ_ALIGNED(v_w, 4) && PZ_ALIGNED(h_first, 4) && PZ_ALIGNED(h_count, 4) && PZ_ALIGNED(v_first, 4) &&
-                   PZ_ALIGNED(v_count, 4),
-               "image_resize_norm: misaligned pointer");
+               who, (long long)h_taps, (long long)v_taps, PZ_OBS_MAX_TAPS, (PZ_OBS_MAX_TAPS - 2) / 6);
+  PZ_CHECK_ARG(PZ_ALIGNED(scratch, 4) && PZ_ALIGNED(out, code ? 1 : 2) && PZ_ALIGNED(lut, 2) &&
+                   PZ_ALIGNED(h_w, 4) && PZ_ALIGNED(v_w, 4) && PZ_ALIGNED(h_first, 4) && PZ_ALIGNED(h_count, 4) &&
+                   PZ_ALIGNED(v_first, 4) && PZ_ALIGNED(v_count, 4),
+               "%s: misaligned pointer", who);
   const int64_t need = pz_image_resize_scratch_bytes(n, H_in, S);
-  PZ_CHECK_ARG(scratch_bytes >= need, "image_resize_norm: scratch has %lld bytes, needs %lld",
-               (long long)scratch_bytes, (long long)need);
-  const int64_t tot_h = n * 3 * H_in * S, tot_v = n * 3 * S * S;
-  PZ_CHECK_ARG(obs_disjoint(scratch, need, out, tot_v * 2) && obs_disjoint(scratch, need, frames, n * 3 * H_in * W_in) &&
-                   obs_disjoint(out, tot_v * 2, frames, n * 3 * H_in * W_in),
-               "image_resize_norm: frames, scratch and out overlap");
+  PZ_CHECK_ARG(scratch_bytes >= need, "%s: scratch has %lld bytes, needs %lld", who, (long long)scratch_bytes,
+               (long long)need);
+  const int64_t tot_h = n * 3 * H_in * S, tot_v = n * 3 * S * S, osz = code ? 1 : 2;
+  const int64_t fbytes = n * 3 * H_in * W_in;
+  PZ_CHECK_ARG(obs_disjoint(scratch, need, out, tot_v * osz) && obs_disjoint(scratch, need, frames, fbytes) &&
+                   obs_disjoint(out, tot_v * osz, frames, fbytes),
+               "%s: frames, scratch and out overlap", who);
   unsigned gh, gv;
-  PZ_CHECK_ARG(obs_grid(tot_h, &gh) && obs_grid(tot_v, &gv), "image_resize_norm: too many elements for one launch");
+  PZ_CHECK_ARG(obs_grid(tot_h, &gh) && obs_grid(tot_v, &gv), "%s: too many elements for one launch", who);
   const Taps th{(const int*)h_first, (const int*)h_count, (const float*)h_w, (int)h_taps};
   const Taps tv{(const int*)v_first, (const int*)v_count, (const float*)v_w, (int)v_taps};
   if (channels_last)
@@ -179,10 +186,31 @@ extern "C" int pz_image_resize_norm(const void* frames, int32_t channels_last, i
     hipLaunchKernelGGL(resize_h_kernel<false>, dim3(gh), dim3(OBS_THREADS), 0, ST, (const uint8_t*)frames,
                        (float*)scratch, tot_h, (int)H_in, (int)W_in, (int)S, th);
   PZ_CHECK_LAUNCH();
-  hipLaunchKernelGGL(resize_v_kernel, dim3(gv), dim3(OBS_THREADS), 0, ST, (const float*)scratch, (bf16_t*)out, tot_v,
-                     (int)H_in, (int)S, tv, (const bf16_t*)lut);
+  if (code)
+    hipLaunchKernelGGL(resize_v_kernel<uint8_t>, dim3(gv), dim3(OBS_THREADS), 0, ST, (const float*)scratch,
+                       (uint8_t*)out, tot_v, (int)H_in, (int)S, tv, (const bf16_t*)lut);
+  else
+    hipLaunchKernelGGL(resize_v_kernel<bf16_t>, dim3(gv), dim3(OBS_THREADS), 0, ST, (const float*)scratch,
+                       (bf16_t*)out, tot_v, (int)H_in, (int)S, tv, (const bf16_t*)lut);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
+}
+
+extern "C" int pz_image_resize_norm(const void* frames, int32_t channels_last, int64_t n, int64_t H_in, int64_t W_in,
+                                    int64_t S, const void* h_first, const void* h_count, const void* h_w,
+                                    int64_t h_taps, const void* v_first, const void* v_count, const void* v_w,
+                                    int64_t v_taps, const void* lut, void* scratch, int64_t scratch_bytes, void* out,
+                                    void* stream) {
+  return resize_launch("image_resize_norm", false, frames, channels_last, n, H_in, W_in, S, h_first, h_count, h_w,
+                       h_taps, v_first, v_count, v_w, v_taps, lut, scratch, scratch_bytes, out, stream);
+}
+
+extern "C" int pz_image_resize_u8(const void* frames, int32_t channels_last, int64_t n, int64_t H_in, int64_t W_in,
+                                  int64_t S, const void* h_first, const void* h_count, const void* h_w, int64_t h_taps,
+                                  const void* v_first, const void* v_count, const void* v_w, int64_t v_taps,
+                                  void* scratch, int64_t scratch_bytes, void* out, void* stream) {
+  return resize_launch("image_resize_u8", true, frames, channels_last, n, H_in, W_in, S, h_first, h_count, h_w, h_taps,
+                       v_first, v_count, v_w, v_taps, nullptr, scratch, scratch_bytes, out, stream);
 }
 
 static int obs_norm_check(const char* who, const void* x, const void* y, int64_t rows, int64_t D, const void* a,

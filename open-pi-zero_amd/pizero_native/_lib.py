@@ -25,6 +25,8 @@ PZ_EPI_DGELU, PZ_EPI_DSILU, PZ_EPI_DGEGLU = 4, 5, 6
 PZ_SUMSQ_PARTS = 2048  # include/pz_abi.h
 PZ_OBS_MAX_TAPS, PZ_OBS_MAX_EXTENT = 64, 16384  # include/pz_abi.h
 PZ_OBS_NORM_BOUND, PZ_OBS_NORM_GAUSSIAN = 0, 1
+# include/pz_abi.h: the ops of pz_image_augment's per-frame mask, in the order they are applied
+PZ_AUG_CROP, PZ_AUG_BRIGHTNESS, PZ_AUG_CONTRAST, PZ_AUG_SATURATION, PZ_AUG_HUE, PZ_AUG_ALL = 1, 2, 4, 8, 16, 31
 
 i64, i32, f32, vp = C.c_int64, C.c_int32, C.c_float, C.c_void_p
 fp = C.POINTER(C.c_float)
@@ -195,13 +197,17 @@ SIGNATURES = {
     "pz_image_resize_norm": [vp, i32, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, vp],
     "pz_proprio_normalize": [vp, vp, i64, i64, vp, vp, i32, vp],
     "pz_action_denormalize": [vp, vp, i64, i64, i64, vp, vp, i32, vp],
+    "pz_image_augment_scratch_bytes": [i64, i64],
+    "pz_image_augment": [vp, i32, i64, i64, vp, vp, i32, vp, vp, i64, vp, vp],
+    "pz_image_resize_u8": [vp, i32, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp],
     "pz_debug_poison_lds": [C.c_uint32, vp],
     "pz_debug_spin": [i64, i64, vp],
     "pz_last_error": [],
     "pz_abi_version": [],
 }
 _RESTYPE = {"pz_last_error": C.c_char_p, "pz_gemm_kernel_name": C.c_char_p, "pz_norm_rows_per_part": i64,
-            "pz_decode_attn_ws_bytes": i64, "pz_lora_wgrad_ws_bytes": i64, "pz_image_resize_scratch_bytes": i64}
+            "pz_decode_attn_ws_bytes": i64, "pz_lora_wgrad_ws_bytes": i64, "pz_image_resize_scratch_bytes": i64,
+            "pz_image_augment_scratch_bytes": i64}
 
 _lib = None
 
@@ -232,7 +238,7 @@ def lib():
 # entry points that enqueue no kernel (everything else takes the stream as its last argument)
 _NO_LAUNCH = {"pz_last_error", "pz_abi_version", "pz_gemm_kernel_name", "pz_norm_rows_per_part",
               "pz_decode_attn_ws_bytes", "pz_lora_wgrad_ws_bytes", "pz_debug_poison_lds",
-              "pz_image_resize_scratch_bytes"}
+              "pz_image_resize_scratch_bytes", "pz_image_augment_scratch_bytes"}
 # test instrument (tests/test_train_loop_gpu.py): with a word set, every launch is preceded on its stream by
 # pz_debug_poison_lds(word), so a kernel reading LDS it did not write sees NaN.  PZ_POISON_LDS=1 turns it on
 # for a whole process (0xffffffff).

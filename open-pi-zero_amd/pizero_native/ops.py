@@ -915,6 +915,90 @@ def image_resize_norm(frames, S, channels_last=True, out=None, scratch=None):
     return out
 
 
+def image_resize_u8(frames, S, channels_last=True, out=None, scratch=None):
+    """image_resize_norm's resize (same kernels, same rounding) with the uint8 code stored instead of its table
+    value: uint8 frames [n, H, W, 3] (channels_last) or [n, 3, H, W] -> uint8 [n, 3, S, S], the input of
+    image_augment for frames that are not at the model's size (resize first, augment after: DESIGN 7e)."""
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.is_contiguous() and frames.is_cuda
+    n = frames.shape[0]
+    if channels_last:
+        H, W, ch = frames.shape[1:]
+    else:
+        ch, H, W = frames.shape[1:]
+    if ch != 3:
+        raise ValueError(f"image_resize_u8: frames must have 3 channels, got shape {tuple(frames.shape)}")
+    dev = frames.device
+    hf, hc, hw, ht = _device_taps(W, S, dev)
+    vf, vc, vw, vt = _device_taps(H, S, dev)
+    need = image_resize_scratch_numel(n, H, S)
+    if scratch is None:
+        scratch = torch.empty(need, device=dev, dtype=torch.float32)
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= need
+    if out is None:
+        out = torch.empty(n, 3, S, S, device=dev, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, 3, S, S)
+    call("pz_image_resize_u8", _p(frames), int(bool(channels_last)), n, H, W, S, _p(hf), _p(hc), _p(hw), ht,
+         _p(vf), _p(vc), _p(vw), vt, _p(scratch), scratch.numel() * 4, _p(out), _st())
+    return out
+
+
+# ---- training-image augmentation (csrc/pz_augment.hip, DESIGN 7e) -------------------------------------------------
+def image_augment_scratch_numel(n, S):
+    """fp32 elements of image_augment's scratch (the partial sums of the contrast's channel means)"""
+    return lib().pz_image_augment_scratch_bytes(int(n), int(S)) // 4
+
+
+def image_augment(frames, params, mask, channels_last=False, out=None, scratch=None):
+    """uint8 frames [n, 3, S, S] (or [n, S, S, 3] with channels_last) -> bf16 [n, 3, S, S]: crop, brightness,
+    contrast, saturation, hue in that order on q / 255 (the TF ops' semantics), requantised with
+    floor(255.5 x) and stored in the model's pixel normalisation (pixel_code_lut).
+
+    ``params`` float32 [n, 8] = box (y1, x1, y2, x2), brightness delta, contrast factor, saturation factor, hue
+    delta; ``mask`` int32 [n], the PZ_AUG_* ops each frame gets (pizero_native.augment.draw_params makes both).
+    Host arrays (numpy / CPU tensors) are uploaded here, and the launch that sums the channel means is skipped when
+    no frame's mask has the contrast; with device tensors nothing is read back, and that launch always runs."""
+    import numpy as np
+
+    from ._lib import PZ_AUG_ALL
+
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.is_contiguous() and frames.is_cuda
+    n = frames.shape[0]
+    S = frames.shape[2]
+    shape = (n, S, S, 3) if channels_last else (n, 3, S, S)
+    if tuple(frames.shape) != shape:
+        want = "[n, S, S, 3]" if channels_last else "[n, 3, S, S]"
+        raise ValueError(f"image_augment: frames must be square with 3 channels, {want}; got shape "
+                         f"{tuple(frames.shape)} (resize first: image_resize_u8)")
+    dev = frames.device
+    if isinstance(params, np.ndarray):
+        params = torch.from_numpy(np.ascontiguousarray(params))
+    if isinstance(mask, np.ndarray):
+        mask = torch.from_numpy(np.ascontiguousarray(mask))
+    if params.dtype != torch.float32 or tuple(params.shape) != (n, 8):
+        raise ValueError(f"image_augment: params must be float32 [{n}, 8], got {params.dtype} {tuple(params.shape)}")
+    if mask.dtype != torch.int32 or tuple(mask.shape) != (n,):
+        raise ValueError(f"image_augment: mask must be int32 [{n}], got {mask.dtype} {tuple(mask.shape)}")
+    if mask.is_cuda:
+        union = PZ_AUG_ALL
+    else:
+        union = int(np.bitwise_or.reduce(mask.numpy())) if n else 0
+        if union & ~PZ_AUG_ALL:
+            raise ValueError(f"image_augment: mask has bits outside PZ_AUG_ALL = {PZ_AUG_ALL}")
+    params = params.to(dev).contiguous()
+    mask = mask.to(dev).contiguous()
+    lut = pixel_code_lut(dev)
+    need = image_augment_scratch_numel(n, S)
+    if scratch is None:
+        scratch = torch.empty(need, device=dev, dtype=torch.float32)
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= need
+    if out is None:
+        out = torch.empty(n, 3, S, S, device=dev, dtype=BF16)
+    assert out.dtype == BF16 and out.is_contiguous() and tuple(out.shape) == (n, 3, S, S)
+    call("pz_image_augment", _p(frames), int(bool(channels_last)), n, S, _p(params), _p(mask), union, _p(lut),
+         _p(scratch), scratch.numel() * 4, _p(out), _st())
+    return out
+
+
 def _norm_args(x, out, a, b, mode):
     assert x.dtype == torch.float32 and x.is_contiguous() and x.is_cuda
     D = x.shape[-1]

@@ -23,6 +23,8 @@ optimizer state dicts, so a resumed run continues bit for bit.
 Data: the OXE/RLDS TensorFlow pipeline is out of scope; the
 agent consumes any iterable of reference-format batches, by default
 ``SyntheticBridgeDataset`` (bridge-shaped random batches, already tokenized).
+What that pipeline does to every training frame after the resize -- random crop and colour jitter
+(src/agent/dataset.py:38-70) -- runs on the device with ``image_augment: True`` (off by default).
 """
 
 from __future__ import annotations
@@ -171,6 +173,22 @@ class TrainAgent:
         if resume:
             self.load_optimizer(resume)
 
+        # training-image augmentation on the device: off by default; the parameters of micro-batch
+        # cnt_batch are drawn on the host from (image_augment_seed, cnt_batch, rank) alone, so a resumed run draws at a
+        # given cnt_batch what the uninterrupted run drew there, and torch's generator (the flow-matching times) is
+        # not touched
+        self.image_augment = bool(cfg_get(cfg, "image_augment", False))
+        if self.image_augment:
+            from pizero_native import augment as A
+
+            kw = cfg_get(cfg, "image_augment_kwargs")
+            self.image_augment_specs = A.parse_kwargs(kw if kw is not None else A.REFERENCE_PRIMARY)
+            self.image_augment_seed = int(cfg_get(cfg, "image_augment_seed", cfg_get(cfg, "seed", 0)))
+            self.image_augment_crop_draws = cfg_get(cfg, "image_augment_crop_draws", "shared")
+            if self.image_augment_crop_draws not in A.CROP_DRAWS:
+                raise ValueError(f"image_augment_crop_draws must be one of {list(A.CROP_DRAWS)}, got "
+                                 f"{self.image_augment_crop_draws!r}")
+
         # in-training validation (train.py:132-160,413-459): on with a val_dataset or a ``data.val`` config node
         self.run_eval = val_dataset is not None or cfg_get(cfg, "data.val") is not None
         self.last_eval = None
@@ -188,12 +206,14 @@ class TrainAgent:
         """train.py:239-247."""
         return sample_fm_time(bsz, self.flow_sampling, self.flow_beta_dist, self.flow_t_max)
 
-    def preprocess_batch(self, batch, split_mask=False, sample_fm_time=True):
+    def preprocess_batch(self, batch, split_mask=False, sample_fm_time=True, augment=False):
         """train.py:271-314 with the per-batch work on the device: the raw batch
         (int64 ids / attention mask, uint8 pixels, fp32 proprio / actions) is copied once, then the
         block mask + positions (vectorised builder, pizero.py:271-324) and the pixel normalisation
         (x/255 - 0.5)/0.5 (vla/processing.py:109-114) are computed on the GPU -- no per-sample host
-        loop, and 1 byte per pixel crosses PCIe instead of 2."""
+        loop, and 1 byte per pixel crosses PCIe instead of 2.  ``augment=True`` (run() passes the config's
+        ``image_augment``; evaluate() never does) puts the uint8 frames through the reference's crop and colour
+        jitter with this micro-batch's (cnt_batch) parameters instead."""
         m = self.model
         dev = self.device
         nb = dict(non_blocking=True)
@@ -201,7 +221,9 @@ class TrainAgent:
         mask, vpos, ppos, apos = m.build_causal_mask_and_position_ids(am, self.dtype)
         pix = batch["pixel_values"].to(dev, **nb)
         img = int(cfg_get(self.cfg, "vision.config.image_size"))
-        if pix.dtype == torch.uint8 and pix.dim() == 4 and tuple(pix.shape[-2:]) != (img, img):
+        if augment:
+            pix = self._augment_frames(pix, img)
+        elif pix.dtype == torch.uint8 and pix.dim() == 4 and tuple(pix.shape[-2:]) != (img, img):
             # frames not yet at the model's resolution: the data pipeline's Lanczos-3 resize (dlimp/utils.py:12-17)
             # and the pixel normalisation in one native op; [B, 3, H, W] as the dataset delivers them
             from pizero_native import ops
@@ -221,6 +243,25 @@ class TrainAgent:
             inputs["t"] = self.sample_fm_time(len(batch["input_ids"])).to(dev, **nb).to(self.dtype)
         return inputs
 
+    def _augment_frames(self, pix, img):
+        """uint8 [B, 3, H, W] on the device -> bf16 [B, 3, img, img]: the resize first where the frames are not at the
+        model's size, then the augmentation, as the reference's pipeline orders them (dlimp/augmentations.py works
+        at the resized resolution)."""
+        from pizero_native import augment as A
+        from pizero_native import ops
+
+        if not self.image_augment:
+            raise ValueError("preprocess_batch(augment=True) needs image_augment: True in the config")
+        if pix.dtype != torch.uint8 or pix.dim() != 4 or pix.shape[1] != 3:
+            raise ValueError("image_augment works on uint8 frames [B, 3, H, W]; got pixel_values of dtype "
+                             f"{pix.dtype}, shape {tuple(pix.shape)} (already normalised frames cannot be augmented)")
+        pix = pix.contiguous()
+        if tuple(pix.shape[-2:]) != (img, img):
+            pix = ops.image_resize_u8(pix, img, channels_last=False)
+        params, op_mask = A.draw_params(self.image_augment_specs, pix.shape[0], self.image_augment_seed,
+                                        self.cnt_batch, self.rank, self.image_augment_crop_draws)
+        return ops.image_augment(pix, params, op_mask, channels_last=False)
+
     def run(self):
         from pizero_native.optim import clip_grad_norm_
 
@@ -229,7 +270,7 @@ class TrainAgent:
         it = iter(self.train_dataloader)
         while self.cnt_update < self.n_updates:
             batch = next(it)
-            inputs = self.preprocess_batch(batch)
+            inputs = self.preprocess_batch(batch, augment=self.image_augment)
             last = (self.cnt_batch + 1) % self.grad_accumulation_steps == 0
             ctx = self.model_meta.no_sync() if (self.multi_gpu and not last) else torch.enable_grad()
             with ctx:
