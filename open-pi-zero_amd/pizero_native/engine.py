@@ -327,11 +327,10 @@ def _merged_weights(fn):
 class Group:
     """Rows of the joint sequence that share one set of mixture weights."""
 
-    def __init__(self, name, prefix, mixtures, T, joint_off, hidden, inter, theta, skip_last, pos_key):
-        self.name, self.prefix, self.mixtures = name, prefix, mixtures
+    def __init__(self, name, prefix, T, joint_off, hidden, inter, theta, skip_last):
+        self.name, self.prefix = name, prefix
         self.T, self.off, self.hid, self.inter, self.theta = T, joint_off, hidden, inter, theta
         self.skip_last = skip_last
-        self.pos_key = pos_key
 
 
 class Engine:
@@ -425,6 +424,35 @@ class Engine:
         if st is None:
             st = self._lora_sites[wnames] = LoraSite(self, wnames)
         return st
+
+    def _linear(self, x, names, W, out, train, fp8=True, gemm=ops.linear, **kw):
+        """out = x W^T of the Linear site ``names`` (fused along N; W their weights).  Training: ops.linear (``gemm``
+        in its place: a q|k|v projection with its RoPE epilogue) + the site's adapter term u B2^T inside the GEMM;
+        returns u (None without adapters), which the backward reads.  Inference: self.lin -- fp8 codes (prepare_fp8)
+        where ``fp8`` allows them, merged weights, no adapter term."""
+        if not train:
+            if fp8:
+                self.lin(x, names[0], W, out, **kw)
+            else:
+                ops.linear(x, W, out, **kw)
+            return None
+        site = self.lora(*names)
+        lo = site.fwd(x) if site is not None else None
+        gemm(x, W, out, lora=lo, **kw)
+        return lo[0] if lo else None
+
+    def _dgrad(self, names, x, u, dy, W, dx, beta, wgrad=None, **kw):
+        """dx = dy W of the Linear site ``names`` (input x, saved u): the adapters' v = dy B2 and their gradients,
+        then the input-gradient GEMM with v A summed inside.  wgrad: the base weights' gradient launches where they go
+        out between the two (the joint q|k|v site)."""
+        site = self.lora(*names)
+        lo = None
+        if site is not None:
+            lo = site.bwd(dy)
+            site.grads(x, u, dy, lo[0], beta)
+        if wgrad is not None:
+            wgrad()
+        ops.linear_dgrad(dy, W, dx, lora=lo, **kw)
 
     def lora_refresh(self):
         """Merged inference weights W + s B A of every adapted Linear (the reference merges on eval(), lora.py:186-199)
@@ -592,26 +620,27 @@ class Engine:
             self._ws[("colsum", dev)] = t
         return t
 
-    def groups(self, tied, active=("vlm", "proprio", "action")):
+    def groups(self, tied, active=("vlm", "proprio", "action"), text=None):
+        """The weight groups of the ``active`` mixtures in joint-token order (the group that holds the action rows
+        last); a group's name also keys its rows / positions in the callers' dicts.  text = q (text generation): the
+        vlm group over q new tokens, every layer run to its end."""
         d = self.d
         out = []
         mp = "joint_model.mixtures."
         if "vlm" in active:
-            out.append(Group("vlm", mp + "vlm.layers.", ["vlm"], d.P, 0, d.gH, d.gI, d.g_theta, True, "vlm"))
+            out.append(Group("vlm", mp + "vlm.layers.", d.P if text is None else text, 0, d.gH, d.gI, d.g_theta,
+                             text is None))
         if tied:
             mix = [m for m in ("proprio", "action") if m in active]
             T = (d.C if "proprio" in mix else 0) + (d.H if "action" in mix else 0)
             if T:
                 off = d.P if "proprio" in mix else d.P + d.C
-                out.append(Group("expert", mp + "action.layers.", mix, T, off, d.aH, d.aI, d.a_theta,
-                                 mix == ["proprio"], "expert"))
+                out.append(Group("expert", mp + "action.layers.", T, off, d.aH, d.aI, d.a_theta, mix == ["proprio"]))
         else:
             if "proprio" in active:
-                out.append(Group("proprio", mp + "proprio.layers.", ["proprio"], d.C, d.P, d.aH, d.aI, d.p_theta,
-                                 True, "proprio"))
+                out.append(Group("proprio", mp + "proprio.layers.", d.C, d.P, d.aH, d.aI, d.p_theta, True))
             if "action" in active:
-                out.append(Group("action", mp + "action.layers.", ["action"], d.H, d.P + d.C, d.aH, d.aI,
-                                 d.a_theta, False, "action"))
+                out.append(Group("action", mp + "action.layers.", d.H, d.P + d.C, d.aH, d.aI, d.a_theta, False))
         return out
 
     # ------------------------------------------------------- second stream --
@@ -666,17 +695,7 @@ class Engine:
         nh, hd = d.vheads, d.vH // d.vheads
         Np = Nt
         layers = []
-
-        def L(x_, key, W, out, site=None, **kw):  # fp8 codes (prepare_fp8) serve inference only
-            if save is None:  # (inference of a LoRA model: W is the merged weight, no adapter term)
-                return self.lin(x_, p + key, W, out, **kw)
-            u = None
-            if site is not None:  # training with adapters: + u B^T inside the GEMM; u saved for the backward
-                u, B2 = site.fwd(x_)
-                kw["lora"] = (u, B2)
-            ops.linear(x_, W, out, **kw)
-            return u
-
+        train = save is not None
         for i in range(d.vL):
             p = f"{vt}encoder.layers.{i}."
             st = {"x": x}
@@ -690,18 +709,16 @@ class Engine:
                 ops.layernorm(x, self.w(p + "layer_norm1.weight"), self.w(p + "layer_norm1.bias"), h1, mu1, r1,
                               d.ln_eps)
             qkv = torch.empty(M, 3 * d.vH, device=dev, dtype=BF16)
-            u_qkv = L(h1, "self_attn.q_proj.weight",
-                      self.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight"), qkv,
-                      site=self.lora(*(p + f"self_attn.{k}_proj.weight" for k in "qkv")),
-                      bias=self.span(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias"))
+            u_qkv = self._linear(h1, [p + f"self_attn.{k}_proj.weight" for k in "qkv"], self.qkv_siglip(p), qkv, train,
+                                 bias=self.span(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias"))
             # fused attention (siglip.py:108-166) in place on the q|k|v rows: O and one fp32
             # log-sum-exp per (head, query) row; no [B, heads, N, N] tensor exists
             O = torch.empty(M, d.vH, device=dev, dtype=BF16)
             lse = torch.empty(B * nh, Np, device=dev, dtype=F32)
             ops.flash_fwd(ops.siglip_flash_args(qkv, O, lse, B, nh, hd, Np))
             xm = torch.empty_like(x)
-            u_o = L(O, "self_attn.out_proj.weight", self.w(p + "self_attn.out_proj.weight"), xm,
-                    site=self.lora(p + "self_attn.out_proj.weight"), bias=self.w(p + "self_attn.out_proj.bias"), resid=x)
+            u_o = self._linear(O, [p + "self_attn.out_proj.weight"], self.w(p + "self_attn.out_proj.weight"), xm, train,
+                               bias=self.w(p + "self_attn.out_proj.bias"), resid=x)
             if save is None and self.w8a8_in(p + "mlp.fc1.weight", M, d.vH):  # fp8: LayerNorm -> codes
                 h2 = self.norm_codes(xm, self.w(p + "layer_norm2.weight"), d.ln_eps, self.w(p + "layer_norm2.bias"))
                 mu2 = r2 = None
@@ -713,11 +730,11 @@ class Engine:
                               d.ln_eps)
             a1 = self._sig_rows(M, dev) if save is not None else None
             g1 = self._sig_rows(M, dev)
-            u_fc1 = L(h2, "mlp.fc1.weight", self.w(p + "mlp.fc1.weight"), g1, site=self.lora(p + "mlp.fc1.weight"),
-                      bias=self.w(p + "mlp.fc1.bias"), epi=PZ_EPI_GELU, aux=a1)
+            u_fc1 = self._linear(h2, [p + "mlp.fc1.weight"], self.w(p + "mlp.fc1.weight"), g1, train,
+                                 bias=self.w(p + "mlp.fc1.bias"), epi=PZ_EPI_GELU, aux=a1)
             xn = torch.empty_like(x)
-            u_fc2 = L(g1, "mlp.fc2.weight", self.w(p + "mlp.fc2.weight"), xn, site=self.lora(p + "mlp.fc2.weight"),
-                      bias=self.w(p + "mlp.fc2.bias"), resid=xm)
+            u_fc2 = self._linear(g1, [p + "mlp.fc2.weight"], self.w(p + "mlp.fc2.weight"), xn, train,
+                                 bias=self.w(p + "mlp.fc2.bias"), resid=xm)
             if save is not None:
                 st.update(u_qkv=u_qkv, u_o=u_o, u_fc1=u_fc1, u_fc2=u_fc2)
                 st.update(h1=h1, mu1=mu1, r1=r1, qkv=qkv, lse=lse, O=O, xm=xm, h2=h2, mu2=mu2, r2=r2, a1=a1, g1=g1)
@@ -729,15 +746,8 @@ class Engine:
         r = torch.empty(M, device=dev, dtype=F32)
         ops.layernorm(x, self.w(vt + "post_layernorm.weight"), self.w(vt + "post_layernorm.bias"), y, mu, r, d.ln_eps)
         img = torch.empty(M, d.proj, device=dev, dtype=BF16)
-        ps = self.lora("multi_modal_projector.linear.weight") if save is not None else None
-        u_proj = None
-        if ps is not None:
-            u_proj, B2 = ps.fwd(y)
-            ops.linear(y, self.w("multi_modal_projector.linear.weight"), img,
-                       bias=self.w("multi_modal_projector.linear.bias"), lora=(u_proj, B2))
-        else:
-            ops.linear(y, self.w("multi_modal_projector.linear.weight"), img,
-                       bias=self.w("multi_modal_projector.linear.bias"))
+        u_proj = self._linear(y, ["multi_modal_projector.linear.weight"], self.w("multi_modal_projector.linear.weight"),
+                              img, train, bias=self.w("multi_modal_projector.linear.bias"))
         if save is not None:
             save["u_proj"] = u_proj
             save.update(layers=layers, x_last=x, y=y, mu=mu, r=r, B=B)
@@ -774,12 +784,7 @@ class Engine:
         if self.rg(nm + "bias"):
             ops.colsum(dimg, self.gw(nm + "bias"), ws, beta=beta)
         dy = torch.empty(M, d.vH, device=dev, dtype=BF16)
-        ps = self.lora(nm + "weight")
-        lo = None
-        if ps is not None:
-            lo = ps.bwd(dimg)
-            ps.grads(sv["y"], sv["u_proj"], dimg, lo[0], beta)
-        ops.linear_dgrad(dimg, self.w(nm + "weight"), dy, lora=lo)
+        self._dgrad([nm + "weight"], sv["y"], sv["u_proj"], dimg, self.w(nm + "weight"), dy, beta)
         dx = torch.empty_like(dy)
         ops.layernorm_bwd(dy, sv["x_last"], self.w(vt + "post_layernorm.weight"), sv["mu"], sv["r"], dx,
                           dw_part=pw, db_part=pb, dx_part=pd)
@@ -800,15 +805,8 @@ class Engine:
             # MLP: x' = xm + fc2(gelu(fc1(ln2(xm))))
             # dgrad through fc2, then the GELU derivative at the saved pre-activation a1
             fc1b = self.rg(p + "mlp.fc1.bias")
-            s_fc2, s_fc1 = self.lora(p + "mlp.fc2.weight"), self.lora(p + "mlp.fc1.weight")
-            s_o = self.lora(p + "self_attn.out_proj.weight")
-            s_qkv = self.lora(*(p + f"self_attn.{k}_proj.weight" for k in "qkv"))
-            lo = None
-            if s_fc2 is not None:
-                lo = s_fc2.bwd(dx)
-                s_fc2.grads(st["g1"], st["u_fc2"], dx, lo[0], beta)
             # plain dgrad GEMM, then the GELU backward (HBM-bound) in place
-            ops.linear_dgrad(dx, self.w(p + "mlp.fc2.weight"), dg, lora=lo)
+            self._dgrad([p + "mlp.fc2.weight"], st["g1"], st["u_fc2"], dx, self.w(p + "mlp.fc2.weight"), dg, beta)
             if fb and fc1b:  # + the fc1 bias gradient from the same pass
                 ops.act_bwd_colsum(dg, st["a1"], dg, PZ_EPI_GELU, ws_act, self.gw(p + "mlp.fc1.bias"), beta=beta)
             else:
@@ -825,11 +823,7 @@ class Engine:
                 ops.linear_wgrad(dg, st["h2"], self.gw(p + "mlp.fc1.weight"), beta=beta)
             if fc1b and not fb:
                 ops.colsum(dg, self.gw(p + "mlp.fc1.bias"), ws, beta=beta)
-            lo = None
-            if s_fc1 is not None:
-                lo = s_fc1.bwd(dg)
-                s_fc1.grads(st["h2"], st["u_fc1"], dg, lo[0], beta)
-            ops.linear_dgrad(dg, self.w(p + "mlp.fc1.weight"), dh, lora=lo)
+            self._dgrad([p + "mlp.fc1.weight"], st["h2"], st["u_fc1"], dg, self.w(p + "mlp.fc1.weight"), dh, beta)
             ops.layernorm_bwd(dh, st["xm"], self.w(p + "layer_norm2.weight"), st["mu2"], st["r2"], dxm, dres=dx,
                               dw_part=pw2, db_part=pb2, dx_part=pd2)
             self._norm_grads(p + "layer_norm2.", pw2, pb2, beta, red)
@@ -841,11 +835,8 @@ class Engine:
                     self._reduce(red, pd2, self.gw(p + "self_attn.out_proj.bias"), beta)
                 else:
                     ops.colsum(dxm, self.gw(p + "self_attn.out_proj.bias"), ws, beta=beta)
-            lo = None
-            if s_o is not None:
-                lo = s_o.bwd(dxm)
-                s_o.grads(st["O"], st["u_o"], dxm, lo[0], beta)
-            ops.linear_dgrad(dxm, self.w(p + "self_attn.out_proj.weight"), dO, lora=lo)
+            self._dgrad([p + "self_attn.out_proj.weight"], st["O"], st["u_o"], dxm,
+                        self.w(p + "self_attn.out_proj.weight"), dO, beta)
             # fused attention backward: dQ | dK | dV straight into the q|k|v gradient rows
             ops.flash_bwd(ops.siglip_flash_args(st["qkv"], st["O"], st["lse"], B, nh, hd, Np, dO=dO, delta=delta,
                                                 dqkv=dqkv))
@@ -859,11 +850,8 @@ class Engine:
                                          beta=beta)
             if all(self.rg(p + f"self_attn.{k}_proj.bias") for k in "qkv"):
                 ops.colsum(dqkv, self.ar.grad_span(qn + "bias", vn + "bias"), ws, beta=beta)
-            lo = None
-            if s_qkv is not None:
-                lo = s_qkv.bwd(dqkv)
-                s_qkv.grads(st["h1"], st["u_qkv"], dqkv, lo[0], beta)
-            ops.linear_dgrad(dqkv, self.qkv_siglip(p), dh, lora=lo)
+            self._dgrad([p + f"self_attn.{k}_proj.weight" for k in "qkv"], st["h1"], st["u_qkv"], dqkv,
+                        self.qkv_siglip(p), dh, beta)
             dxn = torch.empty_like(dx)
             ops.layernorm_bwd(dh, st["x"], self.w(p + "layer_norm1.weight"), st["mu1"], st["r1"], dxn, dres=dxm,
                               dw_part=pw, db_part=pb, dx_part=pdn)
@@ -897,6 +885,31 @@ class Engine:
             self._reduce(red, pw, self.gw(prefix + "weight"), beta)
         if pb is not None and self.rg(prefix + "bias"):
             self._reduce(red, pb, self.gw(prefix + "bias"), beta)
+
+    @staticmethod
+    def _rms_name(g, l, site):
+        if site == "":
+            return g.prefix[: -len("layers.")] + "norm."
+        return f"{g.prefix}{l}." + ("input_layernorm." if site == "in_" else "post_attention_layernorm.")
+
+    def _norm_fwd(self, A, g, x, l, site, h, rstd=None):
+        """h = the norm ``site`` of group g over x: the AdaptiveRMSNorm of its Ada, or (A None) the Gemma RMSNorm.
+        site: "in_" | "post_" of layer l, or "" with l = "norm" (the mixture's final norm)"""
+        if A is not None:
+            A.norm_fwd(x, l, site, g.T, h, rstd)
+        else:
+            ops.rmsnorm(x, self.w(self._rms_name(g, l, site) + "weight"), h, rstd, self.d.rms_eps)
+
+    def _norm_bwd(self, A, g, dh, x, rstd, l, site, dx, dres, beta):
+        """backward of _norm_fwd: dx = d norm(x) (+ dres); the RMSNorm weight gradient from its row partials (an Ada
+        accumulates its modulation gradient rows instead, Ada.weight_grads)"""
+        if A is not None:
+            return A.norm_bwd(dh, x, rstd, l, site, g.T, dx, dres=dres)
+        rpp = ops.rows_per_part()
+        name = self._rms_name(g, l, site)
+        part = torch.empty((x.shape[0] + rpp - 1) // rpp, g.hid, device=x.device, dtype=F32)
+        ops.rmsnorm_bwd(dh, x, self.w(name + "weight"), rstd, dx, dres=dres, dw_part=part)
+        self._norm_grads(name, part, None, beta)
 
     @staticmethod
     def _reduce(red, part, out, beta):
@@ -1007,6 +1020,24 @@ class Engine:
             mask_mode=1, cnt=cnt, prefix=d.P, cond=d.C, rows_per_token=nh,
             dgroups=None if dO is None else [dO.get(g.name) for g in gs], delta=delta, dq=dq, dk=dk, dv=dv)
 
+    def _attn_gemm(self, Q, K, V, S, Os, groups, qoff, Lq, nk, which, cnt, B, export=False):
+        """The GEMM attention path: S = Q K^T per sample into the caller's fp32 scratch S [B, Lq*nh, Lp] (MQA heads
+        stacked as rows), soft-cap + mask softmax (the block mask from cnt or its GeneralMask field ``which``), then
+        O = P V of every group of ``groups`` into Os.  The Lq query tokens start at joint token qoff and see the first
+        nk keys.  Returns (P, tanh(cap) export or None), bf16 [B, Lq*nh, Lp]; export: for the training backward."""
+        d = self.d
+        nh, hd, Lp = d.nh, d.hd, d.Lp
+        ops.gemm(Lq * nh, nk, hd, Q, hd, True, K, hd, True, S, Lp, batch=B, sA=(Lq * nh * hd, 0), sB=(Lp * hd, 0),
+                 sC=(Lq * nh * Lp, 0))
+        Pm = torch.empty(B, Lq * nh, Lp, device=Q.device, dtype=BF16)
+        tc = torch.empty_like(Pm) if export else None
+        ops.attn_softmax(S, Lp, Pm, Lp, B * Lq * nh, nk, 1.0 / math.sqrt(hd), cap=50.0, tcap=tc,
+                         rows_per_batch=Lq * nh, heads=nh, qoff=qoff, **_mask_kw(d, cnt, which))
+        for g in groups:
+            ops.gemm(g.T * nh, hd, Lp, Pm[:, (g.off - qoff) * nh:], Lp, True, V, hd, False, Os[g.name], hd, batch=B,
+                     sA=(Lq * nh * Lp, 0), sB=(Lp * hd, 0), sC=(g.T * nh * hd, 0))
+        return Pm, tc
+
     def _joint_kv(self, B, Lp, dev, save):
         """Joint K/V buffers [nL, B, Lp, hd] for one training forward.  The engine owns one zeroed set
         (the Lp - L pad rows stay zero for the GEMM path; rows < L are rewritten by every forward) and
@@ -1039,86 +1070,67 @@ class Engine:
         M = x.shape[0]
         h = torch.empty_like(x)
         r = torch.empty(M, device=dev, dtype=F32)
-        A = ada.get(g.name) if ada else None
-        if A is not None:
-            A.norm_fwd(x, l, "in_", g.T, h, r)
-        else:
-            ops.rmsnorm(x, self.w(p + "input_layernorm.weight"), h, r, d.rms_eps)
-        # q|k|v projection + RoPE + joint scatter: one 8-phase GEMM whose epilogue rotates and writes
-        # Q / K / V (N1: no [M, 2560] qkv tensor, no split launch); rows too few for the 8-phase
-        # kernel (the action expert's 320) take GEMM + qkv_rope_split (same bits)
-        site = self.lora(*(p + f"self_attn.{k}_proj.weight" for k in "qkv"))
-        lo = site.fwd(h) if site is not None else None
-        if not (self.fuse_qkv_rope and ops.gemm_qkv_rope(h, self.qkv_w(p), pos[g.pos_key], self.rope(g.theta),
-                                                         Qj, Kj, Vj, g.T, nh, hd, L, g.off, Lp, g.off, lora=lo)):
-            W = (nh + 2) * hd
-            qkv = torch.empty(M, W, device=dev, dtype=BF16)
-            ops.linear(h, self.qkv_w(p), qkv, lora=lo)
-            ops.qkv_rope_split(qkv, pos[g.pos_key], self.rope(g.theta), Qj, Kj, Vj, B, g.T, nh, 1, hd, L,
-                               g.off, Lp, g.off)
-        st["g"][g.name] = {"x": x, "h": h, "r": r, "u_qkv": lo[0] if lo else None}
+        self._norm_fwd(ada.get(g.name) if ada else None, g, x, l, "in_", h, r)
 
-    def _post_attn_ada(self, A, g, l, X, gs, Os, dev, keep=True):
-        """_post_attn_train of an adaLN group: AdaptiveRMSNorm after the attention; adaLN-Zero gates both branch
-        outputs before their residual adds (joint_model.py:70-79,117-126), each in the row pass that follows it:
-        o_proj's with the post-attention norm, the MLP's alone.  keep False (inference): no saved pre-activation."""
+        def proj(h, W, _, lora):
+            # q|k|v projection + RoPE + joint scatter: one 8-phase GEMM whose epilogue rotates and writes
+            # Q / K / V (N1: no [M, 2560] qkv tensor, no split launch); rows too few for the 8-phase
+            # kernel (the action expert's 320) take GEMM + qkv_rope_split (same bits)
+            if not (self.fuse_qkv_rope and ops.gemm_qkv_rope(h, W, pos[g.name], self.rope(g.theta), Qj, Kj, Vj, g.T,
+                                                             nh, hd, L, g.off, Lp, g.off, lora=lora)):
+                qkv = torch.empty(M, (nh + 2) * hd, device=dev, dtype=BF16)
+                ops.linear(h, W, qkv, lora=lora)
+                ops.qkv_rope_split(qkv, pos[g.name], self.rope(g.theta), Qj, Kj, Vj, B, g.T, nh, 1, hd, L, g.off, Lp,
+                                   g.off)
+
+        u = self._linear(h, [p + f"self_attn.{k}_proj.weight" for k in "qkv"], self.qkv_w(p), None, True, gemm=proj)
+        st["g"][g.name] = {"x": x, "h": h, "r": r, "u_qkv": u}
+
+    def _post_attn(self, g, l, x, O, A=None, gs=None, plain=False):
+        """One group's o_proj (+ residual), post-attention norm and GeGLU MLP (+ residual) of joint layer l
+        (mixture.py:216-242, paligemma/modules.py:86-95) on the attention output O; returns the layer's output rows.
+        A (an adaLN group): AdaptiveRMSNorm after the attention; adaLN-Zero gates both branch outputs before their
+        residual adds (joint_model.py:70-79,117-126), each in the row pass that follows it: o_proj's with the
+        post-attention norm, the MLP's alone.  gs (training): the activations and the adapters' u are saved in it for
+        the backward; inference keeps no pre-activation and runs the few-row / fp8 forms of the Gemma norm + gate|up.
+        plain: the inference pass behind the GEMM attention (infer_flash False, a GeneralMask), which has always run
+        norm + bf16 GEMMs here -- with fp8 codes prepared too, and for the few rows whose norm the flash path fuses;
+        kept as it is because routing it like the flash path changes its outputs (fp8 for certain)."""
         d = self.d
         p = f"{g.prefix}{l}."
-        x = X[g.name]
-        M = x.shape[0]
-        O = Os[g.name]
+        M, dev = x.shape[0], x.device
+        train = gs is not None
+        zero = A is not None and A.zero
+        o_n, gu_n, dn_n = [p + "self_attn.o_proj.weight"], [p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], \
+            [p + "mlp.down_proj.weight"]
+        nw = None if A is not None else (self.w(p + "post_attention_layernorm.weight"), d.rms_eps)
         xm = torch.empty_like(x)
-        h2 = torch.empty_like(x)
-        r2 = torch.empty(M, device=dev, dtype=F32) if keep else None
-        yo = yd = None
-        if A.zero:
-            yo = torch.empty_like(x)
-            ops.linear(O, self.w(p + "self_attn.o_proj.weight"), yo)
+        yo = torch.empty_like(x) if zero else None
+        u_o = self._linear(O, o_n, self.w(o_n[0]), yo if zero else xm, train, not plain, resid=None if zero else x)
+        hm = torch.empty(M, g.inter, device=dev, dtype=BF16)
+        r2 = torch.empty(M, device=dev, dtype=F32) if train else None
+        norm = None
+        if zero:
+            h2 = torch.empty_like(x)
             A.norm_fwd(x, l, "post_", g.T, h2, r2, y=yo, gate="post_z", xm=xm)
+        elif nw and not train and not plain and self.few_rows(M, g.hid):
+            h2, norm = xm, nw  # few rows (denoise / proprio): RMSNorm fused into the gate|up GEMM
+        elif nw and not train and not plain and self.w8a8_in(gu_n[0], M, g.hid):
+            h2 = self.norm_codes(xm, *nw)  # fp8: RMSNorm -> codes -> W8A8 GeGLU
         else:
-            ops.linear(O, self.w(p + "self_attn.o_proj.weight"), xm, resid=x)
-            A.norm_fwd(xm, l, "post_", g.T, h2, r2)
-        gu = torch.empty(M, 2 * g.inter, device=dev, dtype=BF16) if keep else None
-        hm = torch.empty(M, g.inter, device=dev, dtype=BF16)
-        ops.linear(h2, self.gu_w(p), hm, epi=PZ_EPI_GEGLU, aux=gu)
+            h2 = torch.empty_like(x)
+            self._norm_fwd(A, g, xm, l, "post_", h2, r2)
+        gu = torch.empty(M, 2 * g.inter, device=dev, dtype=BF16) if train else None
+        u_gu = self._linear(h2, gu_n, self.gu_w(p), hm, train, not plain, epi=PZ_EPI_GEGLU, aux=gu, norm=norm)
         xn = torch.empty_like(x)
-        if A.zero:
-            yd = torch.empty_like(x)
-            ops.linear(hm, self.w(p + "mlp.down_proj.weight"), yd)
+        yd = torch.empty_like(x) if zero else None
+        u_dn = self._linear(hm, dn_n, self.w(dn_n[0]), yd if zero else xn, train, not plain,
+                            resid=None if zero else xm)
+        if zero:
             ops.adaln_fwd(xm, A.mod, g.T, d.rms_eps, y=yd, gate=A.biased(l, "final_z"), xm=xn)
-        else:
-            ops.linear(hm, self.w(p + "mlp.down_proj.weight"), xn, resid=xm)
-        if keep:
-            gs.update(O=O, xm=xm, h2=h2, r2=r2, gu=gu, hm=hm, yo=yo, yd=yd, skip=False)
-        X[g.name] = xn
-
-    def _post_attn_train(self, g, l, X, gs, Os, dev):
-        """One group's o_proj (+ residual), post-attention RMSNorm and GeGLU MLP (+ residual) of joint layer l
-        (mixture.py:216-242, paligemma/modules.py:86-95), activations saved in gs for the backward."""
-        d = self.d
-        p = f"{g.prefix}{l}."
-        x = X[g.name]
-        M = x.shape[0]
-        O = Os[g.name]
-        xm = torch.empty_like(x)
-        s_o = self.lora(p + "self_attn.o_proj.weight")
-        s_gu = self.lora(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight")
-        s_dn = self.lora(p + "mlp.down_proj.weight")
-        lo_o = s_o.fwd(O) if s_o is not None else None
-        ops.linear(O, self.w(p + "self_attn.o_proj.weight"), xm, resid=x, lora=lo_o)
-        h2 = torch.empty_like(x)
-        r2 = torch.empty(M, device=dev, dtype=F32)
-        ops.rmsnorm(xm, self.w(p + "post_attention_layernorm.weight"), h2, r2, d.rms_eps)
-        gu = torch.empty(M, 2 * g.inter, device=dev, dtype=BF16)
-        hm = torch.empty(M, g.inter, device=dev, dtype=BF16)
-        lo_gu = s_gu.fwd(h2) if s_gu is not None else None
-        ops.linear(h2, self.gu_w(p), hm, epi=PZ_EPI_GEGLU, aux=gu, lora=lo_gu)
-        xn = torch.empty_like(x)
-        lo_dn = s_dn.fwd(hm) if s_dn is not None else None
-        ops.linear(hm, self.w(p + "mlp.down_proj.weight"), xn, resid=xm, lora=lo_dn)
-        gs.update(O=O, xm=xm, h2=h2, r2=r2, gu=gu, hm=hm, skip=False, u_o=lo_o[0] if lo_o else None,
-                  u_gu=lo_gu[0] if lo_gu else None, u_dn=lo_dn[0] if lo_dn else None)
-        X[g.name] = xn
+        if train:
+            gs.update(O=O, xm=xm, h2=h2, r2=r2, gu=gu, hm=hm, yo=yo, yd=yd, skip=False, u_o=u_o, u_gu=u_gu, u_dn=u_dn)
+        return xn
 
     def _joint_layers_train(self, groups, X, pos, cnt, B, save):
         """joint_model.py:24-304 x nL for the training pass (all mixtures active)."""
@@ -1170,20 +1182,10 @@ class Engine:
                 ops.flash_fwd_probs(self._joint_flash(groups, Qj, Kj, Vj, Os, None, cnt, B, L), Pm, tc, Lp)
                 st["P"], st["tc"], st["O"] = Pm, tc, Os
             else:
-                # S = Q K^T per sample (MQA heads stacked as rows), soft-cap + block-mask softmax, O = P V
                 if S is None:
                     S = torch.empty(B, L * nh, Lp, device=dev, dtype=F32)
-                ops.gemm(L * nh, L, hd, Qj, hd, True, Kj, hd, True, S, Lp, batch=B, sA=(L * nh * hd, 0),
-                         sB=(Lp * hd, 0), sC=(L * nh * Lp, 0))
-                Pm = torch.empty(B, L * nh, Lp, device=dev, dtype=BF16)
-                tc = torch.empty(B, L * nh, Lp, device=dev, dtype=BF16)
-                ops.attn_softmax(S, Lp, Pm, Lp, B * L * nh, L, 1.0 / math.sqrt(hd), cap=50.0, tcap=tc,
-                                 rows_per_batch=L * nh, heads=nh, qoff=0, **_mask_kw(d, cnt, "full"))
-                st["P"], st["tc"] = Pm, tc
-                for g in groups:
-                    if not (last and g.skip_last):
-                        ops.gemm(g.T * nh, hd, Lp, Pm[:, g.off * nh:], Lp, True, Vj, hd, False, Os[g.name], hd, batch=B,
-                                 sA=(L * nh * Lp, 0), sB=(Lp * hd, 0), sC=(g.T * nh * hd, 0))
+                live = [g for g in groups if not (last and g.skip_last)]
+                st["P"], st["tc"] = self._attn_gemm(Qj, Kj, Vj, S, Os, live, 0, L, L, "full", cnt, B, export=True)
                 st["O"] = Os
             if side is not None:
                 side.wait_stream(main)  # the attention outputs
@@ -1196,10 +1198,7 @@ class Engine:
                     gs["skip"] = True
                     continue
                 with self._on(side, g):
-                    if ada and g.name in ada:
-                        self._post_attn_ada(ada[g.name], g, l, X, gs, Os, dev)
-                    else:
-                        self._post_attn_train(g, l, X, gs, Os, dev)
+                    X[g.name] = self._post_attn(g, l, X[g.name], Os[g.name], ada.get(g.name) if ada else None, gs)
             layers.append(st)
             self._chk(f"joint fwd layer {l}", Q=Qj, K=Kj, V=Vj, O=Os, P=st.get("P"), tc=st.get("tc"), X=X)
         if side is not None:  # the expert output and its saved activations are read on the main stream later
@@ -1216,13 +1215,12 @@ class Engine:
         save["joint"] = layers
         return X
 
-    def _mlp_oproj_backward(self, g, gs, p, dX, dO, dXm, beta, rpp, nh, hd, dev, A=None, l=None):
+    def _mlp_oproj_backward(self, g, gs, p, dX, dO, dXm, beta, nh, hd, dev, A=None, l=None):
         """One group's GeGLU MLP + post-attention RMSNorm + o_proj backward of a joint layer
         (paligemma/modules.py:86-95, mixture.py:216-242): dX[g] -> dO[g] (the attention output gradient)
         and dXm[g] (the residual gradient into the input RMSNorm backward)."""
         dx = dres = dX[g.name]
         M = dx.shape[0]
-        part = None if A is not None else torch.empty((M + rpp - 1) // rpp, g.hid, device=dev, dtype=F32)
         if A is not None and A.zero:
             # adaLN-Zero: the MLP branch was gated before its residual add -- the branch gradient is dx * sigma (and the
             # sample's gate gradient), the residual path keeps dx
@@ -1232,14 +1230,8 @@ class Engine:
         # dgrad through down_proj with the GeGLU derivative fused into its epilogue:
         # gu (saved g|u) <- d(gate|up) in place; hm (saved GeGLU output) feeds the down_proj wgrad
         gu = gs["gu"]
-        s_o = self.lora(p + "self_attn.o_proj.weight")
-        s_gu = self.lora(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight")
-        s_dn = self.lora(p + "mlp.down_proj.weight")
-        lo = None
-        if s_dn is not None:
-            lo = s_dn.bwd(dx)
-            s_dn.grads(gs["hm"], gs["u_dn"], dx, lo[0], beta)
-        ops.linear_dgrad(dx, self.w(p + "mlp.down_proj.weight"), gu, epi=PZ_EPI_DGEGLU, aux=gu, lora=lo)
+        self._dgrad([p + "mlp.down_proj.weight"], gs["hm"], gs["u_dn"], dx, self.w(p + "mlp.down_proj.weight"), gu,
+                    beta, epi=PZ_EPI_DGEGLU, aux=gu)
         if self.rg(p + "mlp.down_proj.weight"):
             ops.linear_wgrad(dx, gs["hm"], self.gw(p + "mlp.down_proj.weight"), beta=beta)
         gs["hm"] = None
@@ -1247,18 +1239,10 @@ class Engine:
             ops.linear_wgrad(gu, gs["h2"], self.ar.grad_span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"),
                              beta=beta)
         dh2 = torch.empty(M, g.hid, device=dev, dtype=BF16)
-        lo = None
-        if s_gu is not None:
-            lo = s_gu.bwd(gu)
-            s_gu.grads(gs["h2"], gs["u_gu"], gu, lo[0], beta)
-        ops.linear_dgrad(gu, self.gu_w(p), dh2, lora=lo)
+        self._dgrad([p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], gs["h2"], gs["u_gu"], gu, self.gu_w(p), dh2,
+                    beta)
         dxm = torch.empty_like(dx)
-        if A is not None:
-            A.norm_bwd(dh2, gs["xm"], gs["r2"], l, "post_", g.T, dxm, dres=dres)
-        else:
-            ops.rmsnorm_bwd(dh2, gs["xm"], self.w(p + "post_attention_layernorm.weight"), gs["r2"], dxm, dres=dx,
-                            dw_part=part)
-            self._norm_grads(p + "post_attention_layernorm.", part, None, beta)
+        self._norm_bwd(A, g, dh2, gs["xm"], gs["r2"], l, "post_", dxm, dres, beta)
         # o_proj (adaLN-Zero: its output was gated before the residual add)
         dyo = dxm
         if A is not None and A.zero:
@@ -1267,33 +1251,24 @@ class Engine:
         if self.rg(p + "self_attn.o_proj.weight"):
             ops.linear_wgrad(dyo, gs["O"], self.gw(p + "self_attn.o_proj.weight"), beta=beta)
         o = torch.empty(M, nh * hd, device=dev, dtype=BF16)
-        lo = None
-        if s_o is not None:
-            lo = s_o.bwd(dyo)
-            s_o.grads(gs["O"], gs["u_o"], dyo, lo[0], beta)
-        ops.linear_dgrad(dyo, self.w(p + "self_attn.o_proj.weight"), o, lora=lo)
+        self._dgrad([p + "self_attn.o_proj.weight"], gs["O"], gs["u_o"], dyo, self.w(p + "self_attn.o_proj.weight"), o,
+                    beta)
         dO[g.name] = o
         dXm[g.name] = dxm
 
-    def _qkv_backward(self, g, gs, p, dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta, rpp, nh, hd, dev, A=None, l=None):
+    def _qkv_backward(self, g, gs, p, dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta, nh, hd, dev, A=None, l=None):
         """One group's q|k|v projection + input RMSNorm backward of a joint layer (mixture.py:162-215,
         joint_model.py:170-257 + inverse RoPE): dQ / dK / dV rows of the group -> dX[g]."""
         x = gs["x"]
         M = x.shape[0]
         W = (nh + 2) * hd
         dqkv = torch.empty(M, W, device=dev, dtype=BF16)
-        ops.qkv_rope_split_bwd(None if gs.get("skip") else dQ, dK, dV, pos[g.pos_key], self.rope(g.theta), dqkv,
+        ops.qkv_rope_split_bwd(None if gs.get("skip") else dQ, dK, dV, pos[g.name], self.rope(g.theta), dqkv,
                                B, g.T, nh, 1, hd, L, g.off, Lp, g.off)
         names = [p + f"self_attn.{k}_proj.weight" for k in "qkv"]
         rgs = [self.rg(n) for n in names]
-        site = self.lora(*names)
-        lo = None
-        if site is not None:
-            # adapters: v = dqkv B2 over all three projections (a skipped layer's dQ columns are exactly zero, so its
-            # q adapter gets the zero gradient the reference gives it) and the general input gradient below
-            lo = site.bwd(dqkv)
-            site.grads(gs["h"], gs["u_qkv"], dqkv, lo[0], beta)
-        if gs.get("skip") and site is None:
+        dh = torch.empty(M, g.hid, device=dev, dtype=BF16)
+        if gs.get("skip") and self.lora(*names) is None:
             # last vlm layer: its query rows feed nothing (the post-attention block is skipped), so dQ = 0 exactly --
             # the q_proj gradient is zero (written as such, not computed: pizero.py:231's frozen v_proj and the zero
             # q_proj grad) and only the k|v columns enter the weight / input gradients
@@ -1302,28 +1277,24 @@ class Engine:
             for n, rgk, c0, c1 in zip(names[1:], rgs[1:], (nh * hd, (nh + 1) * hd), ((nh + 1) * hd, W)):
                 if rgk:
                     ops.linear_wgrad(dqkv[:, c0:c1], gs["h"], self.gw(n), beta=beta)
-            dh = torch.empty(M, g.hid, device=dev, dtype=BF16)
             ops.linear_dgrad(dqkv[:, nh * hd:], self.span(names[1], names[2]), dh)
         else:
-            if all(rgs):
-                ops.linear_wgrad(dqkv, gs["h"], self.ar.grad_span(names[0], names[2]), beta=beta)
-            elif rgs[0] and rgs[1]:  # e.g. last-layer vlm v_proj frozen (pizero.py:231)
-                ops.linear_wgrad(dqkv[:, : (nh + 1) * hd], gs["h"], self.ar.grad_span(names[0], names[1]),
-                                 beta=beta)
-            else:
-                for n, rgk, c0, c1 in zip(names, rgs, (0, nh * hd, (nh + 1) * hd), (nh * hd, (nh + 1) * hd, W)):
-                    if rgk:
-                        ops.linear_wgrad(dqkv[:, c0:c1], gs["h"], self.gw(n), beta=beta)
-            dh = torch.empty(M, g.hid, device=dev, dtype=BF16)
-            ops.linear_dgrad(dqkv, self.qkv_w(p), dh, lora=lo)
+            def wgrad():
+                if all(rgs):
+                    ops.linear_wgrad(dqkv, gs["h"], self.ar.grad_span(names[0], names[2]), beta=beta)
+                elif rgs[0] and rgs[1]:  # e.g. last-layer vlm v_proj frozen (pizero.py:231)
+                    ops.linear_wgrad(dqkv[:, : (nh + 1) * hd], gs["h"], self.ar.grad_span(names[0], names[1]),
+                                     beta=beta)
+                else:
+                    for n, rgk, c0, c1 in zip(names, rgs, (0, nh * hd, (nh + 1) * hd), (nh * hd, (nh + 1) * hd, W)):
+                        if rgk:
+                            ops.linear_wgrad(dqkv[:, c0:c1], gs["h"], self.gw(n), beta=beta)
+
+            # adapters: v = dqkv B2 over all three projections (a skipped layer's dQ columns are exactly zero, so its
+            # q adapter gets the zero gradient the reference gives it) and the general input gradient
+            self._dgrad(names, gs["h"], gs["u_qkv"], dqkv, self.qkv_w(p), dh, beta, wgrad=wgrad)
         dxn = torch.empty(M, g.hid, device=dev, dtype=BF16)
-        if A is not None:
-            A.norm_bwd(dh, x, gs["r"], l, "in_", g.T, dxn, dres=dXm.get(g.name))
-        else:
-            part = torch.empty((M + rpp - 1) // rpp, g.hid, device=dev, dtype=F32)
-            ops.rmsnorm_bwd(dh, x, self.w(p + "input_layernorm.weight"), gs["r"], dxn, dres=dXm.get(g.name),
-                            dw_part=part)
-            self._norm_grads(p + "input_layernorm.", part, None, beta)
+        self._norm_bwd(A, g, dh, x, gs["r"], l, "in_", dxn, dXm.get(g.name), beta)
         dX[g.name] = dxn
 
     def _joint_layers_backward(self, groups, dX, pos, cnt, B, sv, beta):
@@ -1331,7 +1302,6 @@ class Engine:
         L, Lp, nh, hd = d.L, d.Lp, d.nh, d.hd
         dev = next(v for v in dX.values() if v is not None).device
         delta = dP = dS = None
-        rpp = ops.rows_per_part()
         # the non-vlm group (action expert, 320 rows at micro-batch 64) runs its MLP / o_proj / q|k|v backward
         # on a second stream while the vlm group's run on the main stream; they meet at the joint attention
         # backward (events both ways).  Tensors one stream allocated and the other reads are record_stream'ed,
@@ -1369,7 +1339,7 @@ class Engine:
                     any_skip = True
                     continue
                 with self._on(side, g):
-                    self._mlp_oproj_backward(g, gs, p, dX, dO, dXm, beta, rpp, nh, hd, dev, ada.get(g.name), l)
+                    self._mlp_oproj_backward(g, gs, p, dX, dO, dXm, beta, nh, hd, dev, ada.get(g.name), l)
                 if side is not None and g.name != "vlm":
                     dO[g.name].record_stream(main)
             if side is not None:
@@ -1432,7 +1402,7 @@ class Engine:
             for g in groups:
                 with self._on(side, g):
                     self._qkv_backward(g, st["g"][g.name], f"{g.prefix}{l}.", dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta,
-                                       rpp, nh, hd, dev, ada.get(g.name), l)
+                                       nh, hd, dev, ada.get(g.name), l)
             # the layer's expert gradients were produced on the side stream: the reducer's communication stream waits
             # for both streams before it reads them (the compute streams keep running; no main <- side join per layer)
             self._chk(f"joint bwd layer {l}", dO=dO, dS=dS, dQ=dQ, dK=dK, dV=dV, dX=dX)
@@ -1446,6 +1416,38 @@ class Engine:
         return dX
 
     # ============================================================ training ==
+    def _expert_rows(self, Xp, e3, B, sp):
+        """{group: input rows} of the expert groups from the proprio rows Xp [B*C, aH] times sp and the action rows e3
+        [B*H, aH] times sqrt(hidden) (joint_model.py:355): a sample's proprio then action rows in the tied group, else
+        one group each.  sp None: Xp is scaled already (an untied proprio group takes it as it is)."""
+        d = self.d
+        sa = math.sqrt(d.aH)
+        if self.m._tied:
+            T = d.C + d.H
+            Xe = torch.empty(B * T, d.aH, device=e3.device, dtype=BF16)
+            ops.copy_rows(Xp, d.aH, d.C * d.aH, Xe, d.aH, T * d.aH, B, d.C, d.aH, scale=sp or 1.0)
+            ops.copy_rows(e3, d.aH, d.H * d.aH, Xe[d.C:], d.aH, T * d.aH, B, d.H, d.aH, scale=sa)
+            return {"expert": Xe}
+        if sp is not None:
+            Xs = torch.empty_like(Xp)
+            ops.copy_rows(Xp, d.aH, 0, Xs, d.aH, 0, 1, B * d.C, d.aH, scale=sp)
+            Xp = Xs
+        Xa = torch.empty_like(e3)
+        ops.copy_rows(e3, d.aH, 0, Xa, d.aH, 0, 1, B * d.H, d.aH, scale=sa)
+        return {"proprio": Xp, "action": Xa}
+
+    def _expert_rows_bwd(self, dX, B, dpe, de3):
+        """inverse of _expert_rows: the expert groups' input gradients into dpe [B*C, aH] and de3 [B*H, aH]"""
+        d = self.d
+        sa = math.sqrt(d.aH)
+        if "expert" in dX:
+            T = d.C + d.H
+            ops.copy_rows(dX["expert"], d.aH, T * d.aH, dpe, d.aH, d.C * d.aH, B, d.C, d.aH, scale=sa)
+            ops.copy_rows(dX["expert"][d.C:], d.aH, T * d.aH, de3, d.aH, d.H * d.aH, B, d.H, d.aH, scale=sa)
+        else:
+            ops.copy_rows(dX["proprio"], d.aH, 0, dpe, d.aH, 0, 1, B * d.C, d.aH, scale=sa)
+            ops.copy_rows(dX["action"], d.aH, 0, de3, d.aH, 0, 1, B * d.H, d.aH, scale=sa)
+
     def train_forward(self, ids, pix, cnt, pos, proprios, actions, t, x0, save):
         """pizero.py:607-661: returns fp32 loss [1]; ``save`` collects activations."""
         d = self.d
@@ -1461,19 +1463,7 @@ class Engine:
         psi = torch.empty(B * d.H, d.A, device=dev, dtype=BF16)
         ops.flow_psi(x0, actions, t, psi, d.sig_min)
         e3 = self.action_embed(psi, t, save)
-        sa = math.sqrt(d.aH)
-        if tied:
-            Xe = torch.empty(B * (d.C + d.H), d.aH, device=dev, dtype=BF16)
-            T = d.C + d.H
-            ops.copy_rows(pe, d.aH, d.C * d.aH, Xe, d.aH, T * d.aH, B, d.C, d.aH, scale=sa)
-            ops.copy_rows(e3, d.aH, d.H * d.aH, Xe[d.C:], d.aH, T * d.aH, B, d.H, d.aH, scale=sa)
-            X = {"vlm": Xv, "expert": Xe}
-        else:
-            Xp = torch.empty(B * d.C, d.aH, device=dev, dtype=BF16)
-            Xa = torch.empty(B * d.H, d.aH, device=dev, dtype=BF16)
-            ops.copy_rows(pe, d.aH, 0, Xp, d.aH, 0, 1, B * d.C, d.aH, scale=sa)
-            ops.copy_rows(e3, d.aH, 0, Xa, d.aH, 0, 1, B * d.H, d.aH, scale=sa)
-            X = {"vlm": Xv, "proprio": Xp, "action": Xa}
+        X = {"vlm": Xv, **self._expert_rows(pe, e3, B, math.sqrt(d.aH))}
         groups = self.groups(tied)
         if d.ada:
             # the time condition (pizero.py:634; no parameters, t is data: no gradient flows into it) and every
@@ -1483,21 +1473,17 @@ class Engine:
             save["cond"] = cond
             save["ada"] = {g.name: Ada(self, g, cond) for g in groups if g.name != "vlm"}
         X = self._joint_layers_train(groups, X, pos, cnt, B, save)
-        ag = "expert" if tied else "action"
+        ag, Tg = groups[-1].name, groups[-1].T
         aoff = d.C if tied else 0
-        Tg = d.C + d.H if tied else d.H
         Xl = X[ag]
         ya = torch.empty_like(Xl)
         ra = torch.empty(Xl.shape[0], device=dev, dtype=F32)
-        if d.ada:
-            save["ada"][ag].norm_fwd(Xl, "norm", "", Tg, ya, ra)
-        else:
-            ops.rmsnorm(Xl, self.w("joint_model.mixtures.action.norm.weight"), ya, ra, d.rms_eps)
+        self._norm_fwd(save["ada"][ag] if d.ada else None, groups[-1], Xl, "norm", "", ya, ra)
         v = torch.empty(B * Tg, 8, device=dev, dtype=BF16)  # columns 0..A-1 written and read (8: 16-B rows)
         ops.small_linear(ya, self.w("action_decoder.weight"), v, bias=self.w("action_decoder.bias"))
         loss = torch.empty(1, device=dev, dtype=F32)
         ops.flow_loss(v[aoff:], 8, Tg * 8, x0, actions, loss, None, None, B, d.H, d.A, d.sig_min)
-        save.update(sv_v=sv_v, ids=ids, cnt=cnt, pos=pos, B=B, prop=prop, pe=pe, tied=tied, Xl=Xl, ya=ya, ra=ra,
+        save.update(sv_v=sv_v, ids=ids, cnt=cnt, pos=pos, B=B, prop=prop, pe=pe, Xl=Xl, ya=ya, ra=ra,
                     x0=x0, x1=actions, v=v, ag=ag, aoff=aoff, Tg=Tg, groups=groups)
         self._chk("train fwd head (action norm, decoder, flow loss)", embed=Xv, ya=ya, v=v, loss=loss)
         return loss
@@ -1509,7 +1495,6 @@ class Engine:
         dev = sv["v"].device
         Tg, aoff = sv["Tg"], sv["aoff"]
         ws = self.colsum_ws(2 * d.aH)
-        rpp = ops.rows_per_part()
         # loss + decoder
         dv = torch.zeros(B * Tg, 8, device=dev, dtype=BF16)
         tmp = torch.empty(1, device=dev, dtype=F32)
@@ -1522,18 +1507,12 @@ class Engine:
         dya = torch.empty(R, d.aH, device=dev, dtype=BF16)
         ops.small_gemm(R, d.aH, d.A, dv, 8, 1, self.w("action_decoder.weight"), d.aH, 1, dya, d.aH)
         dXl = torch.empty_like(dya)
-        ada = sv.get("ada")
-        if ada:
-            for A in ada.values():  # sites that feed nothing (an untied proprio's last layer and final norm) stay 0
-                A.dmod = torch.zeros_like(A.mod)
-            ada[sv["ag"]].norm_bwd(dya, sv["Xl"], sv["ra"], "norm", "", Tg, dXl)
-        else:
-            part = torch.empty((R + rpp - 1) // rpp, d.aH, device=dev, dtype=F32)
-            ops.rmsnorm_bwd(dya, sv["Xl"], self.w("joint_model.mixtures.action.norm.weight"), sv["ra"], dXl,
-                            dw_part=part)
-            self._norm_grads("joint_model.mixtures.action.norm.", part, None, beta)
-        self._chk("train bwd head", dv=dv, dya=dya, dXl=dXl)
+        ada = sv.get("ada") or {}
+        for A in ada.values():  # sites that feed nothing (an untied proprio's last layer and final norm) stay 0
+            A.dmod = torch.zeros_like(A.mod)
         groups = sv["groups"]
+        self._norm_bwd(ada.get(sv["ag"]), groups[-1], dya, sv["Xl"], sv["ra"], "norm", "", dXl, None, beta)
+        self._chk("train bwd head", dv=dv, dya=dya, dXl=dXl)
         dX = {g.name: None for g in groups}
         dX[sv["ag"]] = dXl
         dX = self._joint_layers_backward(groups, dX, sv["pos"], sv["cnt"], B, sv, beta)
@@ -1543,16 +1522,9 @@ class Engine:
             for A in ada.values():
                 A.weight_grads(sv["cond"], self.colsum_ws(A.mod.shape[1]), beta)
         # expert embeddings (joint_model.py:355 scale) -> encoders
-        sa = math.sqrt(d.aH)
         dpe = torch.empty(B * d.C, d.aH, device=dev, dtype=BF16)
         de3 = torch.empty(B * d.H, d.aH, device=dev, dtype=BF16)
-        if sv["tied"]:
-            T = d.C + d.H
-            ops.copy_rows(dX["expert"], d.aH, T * d.aH, dpe, d.aH, d.C * d.aH, B, d.C, d.aH, scale=sa)
-            ops.copy_rows(dX["expert"][d.C:], d.aH, T * d.aH, de3, d.aH, d.H * d.aH, B, d.H, d.aH, scale=sa)
-        else:
-            ops.copy_rows(dX["proprio"], d.aH, 0, dpe, d.aH, 0, 1, B * d.C, d.aH, scale=sa)
-            ops.copy_rows(dX["action"], d.aH, 0, de3, d.aH, 0, 1, B * d.H, d.aH, scale=sa)
+        self._expert_rows_bwd(dX, B, dpe, de3)
         if self.rg("proprio_encoder.weight"):
             ops.small_gemm(d.aH, d.Pd, B * d.C, dpe, 1, d.aH, sv["prop"], d.Pd, 1, self.gw("proprio_encoder.weight"),
                            d.Pd, beta=beta)
@@ -1613,32 +1585,24 @@ class Engine:
         Xv = torch.empty(B * d.P, d.gH, device=dev, dtype=BF16)
         ops.copy_rows(Ev.reshape(B * d.P, d.gH), d.gH, 0, Xv, d.gH, 0, 1, B * d.P, d.gH, scale=math.sqrt(d.gH))
         T = d.C + d.H
-        sa = math.sqrt(d.aH)
-        Xe = torch.empty(B * T, d.aH, device=dev, dtype=BF16)
-        ops.copy_rows(Ep.reshape(B * d.C, d.aH), d.aH, d.C * d.aH, Xe, d.aH, T * d.aH, B, d.C, d.aH, scale=sa)
-        ops.copy_rows(Ea.reshape(B * d.H, d.aH), d.aH, d.H * d.aH, Xe[d.C:], d.aH, T * d.aH, B, d.H, d.aH, scale=sa)
+        Xe = self._expert_rows(Ep.reshape(B * d.C, d.aH), Ea.reshape(B * d.H, d.aH), B, math.sqrt(d.aH))
         groups = self.groups(True)
         save = {}
-        X = self._joint_layers_train(groups, {"vlm": Xv, "expert": Xe}, pos, cnt, B, save)
+        X = self._joint_layers_train(groups, {"vlm": Xv, **Xe}, pos, cnt, B, save)
         Xl = X["expert"]
         ya = torch.empty_like(Xl)
         ra = torch.empty(Xl.shape[0], device=dev, dtype=F32)
-        ops.rmsnorm(Xl, self.w("joint_model.mixtures.action.norm.weight"), ya, ra, d.rms_eps)
+        self._norm_fwd(None, groups[-1], Xl, "norm", "", ya, ra)
         dya = torch.zeros_like(ya)  # proprio rows are not outputs (joint_model.py:375-380 skip list)
         ops.copy_rows(dout.reshape(B * d.H, d.aH).to(BF16), d.aH, d.H * d.aH, dya[d.C:], d.aH, T * d.aH, B, d.H, d.aH)
-        rpp = ops.rows_per_part()
         dXl = torch.empty_like(dya)
-        part = torch.empty((B * T + rpp - 1) // rpp, d.aH, device=dev, dtype=F32)
-        ops.rmsnorm_bwd(dya, Xl, self.w("joint_model.mixtures.action.norm.weight"), ra, dXl, dw_part=part)
-        self._norm_grads("joint_model.mixtures.action.norm.", part, None, beta)
+        self._norm_bwd(None, groups[-1], dya, Xl, ra, "norm", "", dXl, None, beta)
         dX = self._joint_layers_backward(groups, {"vlm": None, "expert": dXl}, pos, cnt, B, save, beta)
         dEv = torch.empty(B, d.P, d.gH, device=dev, dtype=BF16)
         ops.copy_rows(dX["vlm"], d.gH, 0, dEv.view(B * d.P, d.gH), d.gH, 0, 1, B * d.P, d.gH, scale=math.sqrt(d.gH))
         dEp = torch.empty(B, d.C, d.aH, device=dev, dtype=BF16)
         dEa = torch.empty(B, d.H, d.aH, device=dev, dtype=BF16)
-        ops.copy_rows(dX["expert"], d.aH, T * d.aH, dEp.view(B * d.C, d.aH), d.aH, d.C * d.aH, B, d.C, d.aH, scale=sa)
-        ops.copy_rows(dX["expert"][d.C:], d.aH, T * d.aH, dEa.view(B * d.H, d.aH), d.aH, d.H * d.aH, B, d.H, d.aH,
-                      scale=sa)
+        self._expert_rows_bwd(dX, B, dEp.view(B * d.C, d.aH), dEa.view(B * d.H, d.aH))
         out = torch.empty(B, d.H, d.aH, device=dev, dtype=BF16)
         ops.copy_rows(ya[d.C:], d.aH, T * d.aH, out.view(B * d.H, d.aH), d.aH, d.H * d.aH, B, d.H, d.aH)
         return out, {"vlm": dEv, "proprio": dEp, "action": dEa}
@@ -1677,6 +1641,67 @@ class Engine:
         ops.copy_rows(pe, d.aH, 0, Xp, d.aH, 0, 1, B * d.C, d.aH, scale=math.sqrt(d.aH))
         return Xp
 
+    def _qkv_infer(self, g, l, x, pos, Q, Kj, Vj, B, Lq, qo, ko, route, A=None, kv_only=False, gemv=None, cs=None):
+        """One group's input norm + q|k|v projection + RoPE (table cs; default: the group's own) of joint layer l in an
+        inference pass, its rows
+        scattered to query tokens [qo, qo + g.T) of Q [B, Lq, nh*hd] and to rows [ko, ko + g.T) of the K / V caches.
+        kv_only (the last layer of a prefix pass): only K/V are consumed downstream (pizero.py:451, skipped
+        post-attn).  gemv: take the one-launch GEMV (default: wherever gemv_ok and the norm is the Gemma RMSNorm).
+        route names what the passes do differently with the same rows (unmeasured against each other):
+          "prefix"  prefill: fp8 codes from the norm for > 64 rows, the 8-phase GEMM with the RoPE epilogue
+          "decode"  denoise_step: <= 64 rows through the few-row kernels with the norm fused
+          "plain"   text_forward, the adaLN expert: norm, bf16 GEMM, RoPE split -- never fp8 codes"""
+        d = self.d
+        nh, hd, Lp = d.nh, d.hd, Kj.shape[1]
+        p = f"{g.prefix}{l}."
+        M, K = x.shape
+        key = p + "self_attn.q_proj.weight"
+        nw = None if A is not None else (self.w(p + "input_layernorm.weight"), d.rms_eps)
+        if gemv is None:
+            gemv = A is None and self.gemv_ok(M, K)
+
+        def rope():  # (a table not built yet is built where the pass first rotates, after its norm)
+            return cs if cs is not None else self.rope(g.theta)
+
+        if gemv:  # one launch: RMSNorm + q|k|v GEMV + RoPE + Q / K-cache / V-cache scatter
+            if kv_only:
+                ops.gemv_qkv_rope(x, self.span(p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"), pos,
+                                  rope(), None, Kj, Vj, g.T, 0, hd, Lq, qo, Lp, ko, norm=nw)
+            else:
+                ops.gemv_qkv_rope(x, self.qkv_w(p), pos, rope(), Q, Kj, Vj, g.T, nh, hd, Lq, qo, Lp, ko, norm=nw)
+            return
+        qkv = None
+        # the decode pass alone fuses the norm of its 9..64 non-GEMV rows; the prefix pass normalises them in a launch
+        if route == "decode" and self.few_rows(M, K):
+            W, sc = self._qkv_w_f8(p)
+            if self.fuse_qkv_rope and ops.gemm_qkv_rope(x, W, pos, rope(), Q, Kj, Vj, g.T, nh, hd, Lq, qo, Lp, ko,
+                                                        norm=nw, w_scale=sc):
+                return  # C5's 50-row chunk: RMSNorm + skinny-64 q|k|v (bf16 or W8A16) + RoPE + scatter in one launch
+            qkv = torch.empty(M, (nh + 2) * hd, device=x.device, dtype=BF16)
+            self.lin(x, key, self.qkv_w(p), qkv, norm=nw)  # RMSNorm fused into the q|k|v GEMM
+        # the prefix pass alone takes fp8 codes straight from the norm (C5); > 64 decode rows are quantised inside lin
+        elif route == "prefix" and not kv_only and self.w8a8_in(key, M, K):
+            qkv = torch.empty(M, (nh + 2) * hd, device=x.device, dtype=BF16)
+            self.lin(self.norm_codes(x, *nw), key, self.qkv_w(p), qkv)  # q|k|v W8A8 on the fp8 MFMA
+        else:
+            h = torch.empty_like(x)
+            self._norm_fwd(A, g, x, l, "in_", h)
+            # the prefix pass alone has the 8-phase GEMM rotate and scatter: many rows (B >= 16), bf16 weights
+            if route == "prefix" and not kv_only and self.fuse_qkv_rope and not (self.f8 and key in self.f8) and \
+                    ops.gemm_qkv_rope(h, self.qkv_w(p), pos, rope(), Q, Kj, Vj, g.T, nh, hd, Lq, qo, Lp, ko):
+                return
+            qkv = torch.empty(M, (nh + 2) * hd, device=x.device, dtype=BF16)
+            if kv_only:
+                kv = torch.empty(M, 2 * hd, device=x.device, dtype=BF16)
+                ops.linear(h, self.span(p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"), kv)
+                ops.copy_rows(kv, 2 * hd, 0, qkv[:, nh * hd:], (nh + 2) * hd, 0, 1, M, 2 * hd)
+                Q = None
+            elif route == "plain":  # text generation keeps bf16 q|k|v weights with fp8 codes prepared
+                ops.linear(h, self.qkv_w(p), qkv)
+            else:
+                self.lin(h, key, self.qkv_w(p), qkv)
+        ops.qkv_rope_split(qkv, pos, rope(), Q, Kj, Vj, B, g.T, nh, 1, hd, Lq, qo, Lp, ko)
+
     @_merged_weights
     def prefill(self, ids, pix, cnt, vpos, ppos, proprios, kcache, vcache, with_proprio=True):
         """pizero.py:430-451: SigLIP + prefix pass over {vlm, proprio}; writes post-RoPE K/V caches.
@@ -1685,89 +1710,37 @@ class Engine:
         d = self.d
         dev = pix.device
         B = ids.shape[0]
-        nh, hd, Lp = d.nh, d.hd, d.Lp
+        nh, hd = d.nh, d.hd
         L1 = d.P + (d.C if with_proprio else 0)
         img = self.siglip_forward(pix, None)
-        Xv = self.embed_prefix(ids, img)
-        Xp = None
+        groups = self.groups(self.m._tied, active=("vlm", "proprio") if with_proprio else ("vlm",))
+        X, pos = {"vlm": self.embed_prefix(ids, img)}, {"vlm": vpos}
         if with_proprio:
-            Xp = self._proprio_rows(proprios, B, dev)
-        tied = self.m._tied
-        pprefix = "joint_model.mixtures." + ("action" if tied else "proprio") + ".layers."
-        groups = [Group("vlm", "joint_model.mixtures.vlm.layers.", ["vlm"], d.P, 0, d.gH, d.gI, d.g_theta, True, "vlm"),
-                  Group("proprio", pprefix, ["proprio"], d.C, d.P, d.aH, d.aI, d.p_theta if not tied else d.a_theta,
-                        True, "proprio")][: 2 if with_proprio else 1]
-        X = {"vlm": Xv, "proprio": Xp}
-        pos = {"vlm": vpos, "proprio": ppos}
+            X[groups[1].name], pos[groups[1].name] = self._proprio_rows(proprios, B, dev), ppos
         Q = torch.empty(B, L1, nh * hd, device=dev, dtype=BF16)
-        S = Pm = None
+        S = None
+        flash = self.infer_flash and not isinstance(cnt, GeneralMask)
         for l in range(d.nL):
             last = l == d.nL - 1
             Kj, Vj = kcache[l], vcache[l]
-            hs = {}
             for g in groups:
-                p = f"{g.prefix}{l}."
-                x = X[g.name]
-                M = x.shape[0]
-                if self.gemv_ok(M, x.shape[1]):  # few rows (the proprio token): one fused launch
-                    if last:
-                        self._kv_only_gemv(x, p, pos[g.pos_key], g, Kj, Vj, L1, Lp)
-                    else:
-                        ops.gemv_qkv_rope(x, self.qkv_w(p), pos[g.pos_key], self.rope(g.theta), Q, Kj, Vj, g.T, nh,
-                                          hd, L1, g.off, Lp, g.off,
-                                          norm=(self.w(p + "input_layernorm.weight"), d.rms_eps))
-                    continue
-                if not last and self.w8a8_in(p + "self_attn.q_proj.weight", M, x.shape[1]):
-                    # fp8 (C5): input RMSNorm straight to e4m3 codes, q|k|v W8A8 on the fp8 MFMA, RoPE + scatter
-                    qkv = torch.empty(M, (nh + 2) * hd, device=dev, dtype=BF16)
-                    self.lin(self.norm_codes(x, self.w(p + "input_layernorm.weight"), d.rms_eps),
-                             p + "self_attn.q_proj.weight", self.qkv_w(p), qkv)
-                    ops.qkv_rope_split(qkv, pos[g.pos_key], self.rope(g.theta), Q, Kj, Vj, B, g.T, nh, 1, hd, L1,
-                                       g.off, Lp, g.off)
-                    continue
-                h = torch.empty_like(x)
-                ops.rmsnorm(x, self.w(p + "input_layernorm.weight"), h, None, d.rms_eps)
-                if last:  # only K/V are consumed downstream (pizero.py:451, skipped post-attn)
-                    kv = torch.empty(M, 2 * hd, device=dev, dtype=BF16)
-                    ops.linear(h, self.span(p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"), kv)
-                    qkv = torch.empty(M, (nh + 2) * hd, device=dev, dtype=BF16)
-                    ops.copy_rows(kv, 2 * hd, 0, qkv[:, nh * hd:], (nh + 2) * hd, 0, 1, M, 2 * hd)
-                    ops.qkv_rope_split(qkv, pos[g.pos_key], self.rope(g.theta), None, Kj, Vj, B, g.T, nh, 1, hd, L1,
-                                       g.off, Lp, g.off)
-                    continue
-                hs[g.name] = h
-                if self.fuse_qkv_rope and not (self.f8 and (p + "self_attn.q_proj.weight") in self.f8) and \
-                        ops.gemm_qkv_rope(h, self.qkv_w(p), pos[g.pos_key], self.rope(g.theta), Q, Kj, Vj, g.T, nh, hd,
-                                          L1, g.off, Lp, g.off):
-                    continue  # many rows (B >= 16): projection + RoPE + scatter in one 8-phase GEMM
-                qkv = torch.empty(M, (nh + 2) * hd, device=dev, dtype=BF16)
-                self.lin(h, p + "self_attn.q_proj.weight", self.qkv_w(p), qkv)
-                ops.qkv_rope_split(qkv, pos[g.pos_key], self.rope(g.theta), Q, Kj, Vj, B, g.T, nh, 1, hd, L1, g.off,
-                                   Lp, g.off)
+                self._qkv_infer(g, l, X[g.name], pos[g.name], Q, Kj, Vj, B, L1, g.off, g.off,
+                                "prefix", kv_only=last)
             if last:
                 break
-            if self.infer_flash and not isinstance(cnt, GeneralMask):  # fused attention over the L1 prefix keys
-                Os = {g.name: torch.empty(B * g.T, nh * hd, device=dev, dtype=BF16) for g in groups}
+            Os = {g.name: torch.empty(B * g.T, nh * hd, device=dev, dtype=BF16) for g in groups}
+            if flash:  # fused attention over the L1 prefix keys
                 fa = self._attn_flash_infer(Q, Kj, Vj, [(g.off, g.T, Os[g.name]) for g in groups], L1, L1, 0, cnt, B)
                 if self.f8 is not None and hd == 256:
                     self._flash_f8(fa, Q, Kj, Vj, B, L1 * nh, L1)  # fp8 MFMA attention (C5, configs[4])
                 else:
                     ops.flash_fwd(fa)
-                for g in groups:
-                    p = f"{g.prefix}{l}."
-                    X[g.name] = self._post_attn_O(g, p, X[g.name], Os[g.name])
-                continue
-            if S is None:
-                S = torch.empty(B, L1 * nh, Lp, device=dev, dtype=F32)
-                Pm = torch.empty(B, L1 * nh, Lp, device=dev, dtype=BF16)
-            ops.gemm(L1 * nh, L1, hd, Q, hd, True, Kj, hd, True, S, Lp, batch=B, sA=(L1 * nh * hd, 0),
-                     sB=(Lp * hd, 0), sC=(L1 * nh * Lp, 0))
-            ops.attn_softmax(S, Lp, Pm, Lp, B * L1 * nh, L1, 1.0 / math.sqrt(hd), cap=50.0,
-                             rows_per_batch=L1 * nh, heads=nh, qoff=0, **_mask_kw(d, cnt, "itp"))
+            else:
+                if S is None:
+                    S = torch.empty(B, L1 * nh, d.Lp, device=dev, dtype=F32)
+                self._attn_gemm(Q, Kj, Vj, S, Os, groups, 0, L1, L1, "itp", cnt, B)
             for g in groups:
-                p = f"{g.prefix}{l}."
-                x = X[g.name]
-                X[g.name] = self._post_attn(g, p, x, Pm, Vj, B, L1, Lp)
+                X[g.name] = self._post_attn(g, l, X[g.name], Os[g.name], plain=not flash)
         return kcache, vcache
 
     # ========================================================= text generation ==
@@ -1791,30 +1764,23 @@ class Engine:
         img = table if pix is None else self.siglip_forward(pix, None)
         X = torch.empty(B * q, d.gH, device=dev, dtype=BF16)
         ops.embed_merge(ids, table, img, X, n_img, d.image_token, d.pad_token, math.sqrt(d.gH), 1.0)
-        g = Group("vlm", "joint_model.mixtures.vlm.layers.", ["vlm"], q, 0, d.gH, d.gI, d.g_theta, False, "vlm")
+        g, = self.groups(False, active=("vlm",), text=q)
         Q = torch.empty(B, q, nh * hd, device=dev, dtype=BF16)
         O = torch.empty(B * q, nh * hd, device=dev, dtype=BF16)
-        few = self.gemv_ok(B * q, d.gH) and q * nh <= 32
+        few = self.gemv_ok(B * q, d.gH) and q * nh <= 32  # (pz_decode_attn's one 32-row tile)
         cs = self.rope(g.theta, maxpos)
         x = X
         for l in range(d.nL):
-            p = f"{g.prefix}{l}."
             Kl, Vl = kc[l], vc[l]
+            self._qkv_infer(g, l, x, pos, Q, Kl, Vl, B, q, 0, start, "plain", gemv=few, cs=cs)
             if few:
-                ops.gemv_qkv_rope(x, self.qkv_w(p), pos, cs, Q, Kl, Vl, q, nh, hd, q, 0, Lcap, start,
-                                  norm=(self.w(p + "input_layernorm.weight"), d.rms_eps))
                 ops.decode_attn(Q, q, 0, Kl, Vl, O, B, nh, q, nk, 1.0 / math.sqrt(hd), 50.0, None, 0, 0, start)
             else:
-                h = torch.empty_like(x)
-                ops.rmsnorm(x, self.w(p + "input_layernorm.weight"), h, None, d.rms_eps)
-                qkv = torch.empty(B * q, (nh + 2) * hd, device=dev, dtype=BF16)
-                ops.linear(h, self.qkv_w(p), qkv)
-                ops.qkv_rope_split(qkv, pos, cs, Q, Kl, Vl, B, q, nh, 1, hd, q, 0, Lcap, start)
                 ops.flash_fwd(ops.flash_args(
                     B, 1, q * nh, nk, hd, Q, (hd, q * nh * hd, 0), Kl, (hd, Lcap * hd, 0), Vl, (hd, Lcap * hd, 0),
                     [(0, O, q * nh * hd, hd)], 0, None, 1.0 / math.sqrt(hd), cap=50.0, mask_mode=0,
                     rows_per_token=nh, key_split=True))
-            x = self._post_attn_O(g, p, x, O)
+            x = self._post_attn(g, l, x, O)
         nw = "joint_model.mixtures.vlm.norm.weight"
         if nw in self.ar.slots:
             y = torch.empty_like(x)
@@ -1823,13 +1789,6 @@ class Engine:
         logits = torch.empty(B * q, table.shape[0], device=dev, dtype=BF16)
         ops.linear(x, table, logits)
         return logits.view(B, q, -1)
-
-    def _kv_only_gemv(self, x, p, pos, g, Kj, Vj, L1, Lp):
-        """last prefill layer, few rows: only the k|v projection (+RoPE on k) is consumed"""
-        d = self.d
-        ops.gemv_qkv_rope(x, self.span(p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"), pos,
-                          self.rope(g.theta), None, Kj, Vj, g.T, 0, d.hd, L1, g.off, Lp, g.off,
-                          norm=(self.w(p + "input_layernorm.weight"), d.rms_eps))
 
     def _flash_f8(self, fa, Q, K, V, B, nq, nk):
         """the joint attention of fa on the fp8 MFMA: Q rows / key rows quantised per row, V^T per head dim
@@ -1857,53 +1816,12 @@ class Engine:
             mask_mode=1, cnt=cnt, prefix=d.P, cond=d.C, rows_per_token=nh, mask_row0=tok0 * nh,
             key_split=True)
 
-    def _post_attn_O(self, g, p, x, O):
-        """o_proj (+resid), post-attention RMSNorm, GeGLU MLP (+resid) of one mixture."""
-        d = self.d
-        M = x.shape[0]
-        dev = x.device
-        xm = torch.empty_like(x)
-        self.lin(O, p + "self_attn.o_proj.weight", self.w(p + "self_attn.o_proj.weight"), xm, resid=x)
-        hm = torch.empty(M, g.inter, device=dev, dtype=BF16)
-        if self.few_rows(M, x.shape[1]):  # few rows (denoise / proprio): RMSNorm fused into the gate|up GEMM
-            self.lin(xm, p + "mlp.gate_proj.weight", self.gu_w(p), hm, epi=PZ_EPI_GEGLU,
-                     norm=(self.w(p + "post_attention_layernorm.weight"), d.rms_eps))
-        elif self.w8a8_in(p + "mlp.gate_proj.weight", M, x.shape[1]):  # fp8: RMSNorm -> codes -> W8A8 GeGLU
-            self.lin(self.norm_codes(xm, self.w(p + "post_attention_layernorm.weight"), d.rms_eps),
-                     p + "mlp.gate_proj.weight", self.gu_w(p), hm, epi=PZ_EPI_GEGLU)
-        else:
-            h2 = torch.empty_like(x)
-            ops.rmsnorm(xm, self.w(p + "post_attention_layernorm.weight"), h2, None, d.rms_eps)
-            self.lin(h2, p + "mlp.gate_proj.weight", self.gu_w(p), hm, epi=PZ_EPI_GEGLU)
-        xn = torch.empty_like(x)
-        self.lin(hm, p + "mlp.down_proj.weight", self.w(p + "mlp.down_proj.weight"), xn, resid=xm)
-        return xn
-
-    def _post_attn(self, g, p, x, Pm, Vj, B, Lq, Lp, qrow0=None):
-        d = self.d
-        nh, hd = d.nh, d.hd
-        M = x.shape[0]
-        dev = x.device
-        q0 = g.off if qrow0 is None else qrow0
-        O = torch.empty(M, nh * hd, device=dev, dtype=BF16)
-        ops.gemm(g.T * nh, hd, Lp, Pm[:, q0 * nh:], Lp, True, Vj, hd, False, O, hd, batch=B,
-                 sA=(Lq * nh * Lp, 0), sB=(Lp * hd, 0), sC=(g.T * nh * hd, 0))
-        xm = torch.empty_like(x)
-        ops.linear(O, self.w(p + "self_attn.o_proj.weight"), xm, resid=x)
-        h2 = torch.empty_like(x)
-        ops.rmsnorm(xm, self.w(p + "post_attention_layernorm.weight"), h2, None, d.rms_eps)
-        hm = torch.empty(M, g.inter, device=dev, dtype=BF16)
-        ops.linear(h2, self.gu_w(p), hm, epi=PZ_EPI_GEGLU)
-        xn = torch.empty_like(x)
-        ops.linear(hm, self.w(p + "mlp.down_proj.weight"), xn, resid=xm)
-        return xn
-
     @_merged_weights
     def denoise_step(self, action, t, apos, cnt, kcache, vcache, B):
         """One Euler step of pizero.py:461-481 against the cached vlm+proprio K/V."""
         d = self.d
         dev = action.device
-        nh, hd, Lp, L = d.nh, d.hd, d.Lp, d.L
+        nh, hd, L = d.nh, d.hd, d.L
         # the step's glue in two launches (pz_action_in / pz_action_out, bit-identical to cast + Linear + time
         # embedding and RMSNorm + decoder + Euler; PZ_FUSED_GLUE=0: the separate kernels)
         glue = (d.aH <= 1024 and d.aH % 8 == 0 and d.A <= 8 and os.environ.get("PZ_FUSED_GLUE", "1") != "0" and
@@ -1929,50 +1847,23 @@ class Engine:
             e3 = self.action_embed(psi, t, None)
             x = torch.empty_like(e3)
             ops.copy_rows(e3, d.aH, 0, x, d.aH, 0, 1, B * d.H, d.aH, scale=math.sqrt(d.aH))
-        g = Group("action", "joint_model.mixtures.action.layers.", ["action"], d.H, d.P + d.C, d.aH, d.aI, d.a_theta,
-                  False, "action")
+        g, = self.groups(self.m._tied, active=("action",))
         Q = torch.empty(B, d.H, nh * hd, device=dev, dtype=BF16)
-        S = Pm = O = None
+        O = torch.empty(B * d.H, nh * hd, device=dev, dtype=BF16)
+        S = None
+        flash = self.infer_flash and not isinstance(cnt, GeneralMask)
         for l in range(d.nL):
-            p = f"{g.prefix}{l}."
             Kj, Vj = kcache[l], vcache[l]
-            M = x.shape[0]
-            nrm = (self.w(p + "input_layernorm.weight"), d.rms_eps)
-            if self.gemv_ok(M, d.aH):  # one launch: RMSNorm + q|k|v GEMV + RoPE + Q / K-cache / V-cache scatter
-                ops.gemv_qkv_rope(x, self.qkv_w(p), apos, self.rope(g.theta), Q, Kj, Vj, d.H, nh, hd, d.H, 0, Lp,
-                                  g.off, norm=nrm)
-            elif self.fuse_qkv_rope and self.few_rows(M, d.aH) and \
-                    ops.gemm_qkv_rope(x, self._qkv_w_f8(p)[0], apos, self.rope(g.theta), Q, Kj, Vj, d.H, nh, hd, d.H,
-                                      0, Lp, g.off, norm=nrm, w_scale=self._qkv_w_f8(p)[1]):
-                pass  # C5's 50-row chunk: RMSNorm + skinny-64 q|k|v (bf16 or W8A16) + RoPE + scatter in one launch
-            else:
-                qkv = torch.empty(M, (nh + 2) * hd, device=dev, dtype=BF16)
-                if self.few_rows(M, d.aH):  # RMSNorm fused into the q|k|v GEMM
-                    self.lin(x, p + "self_attn.q_proj.weight", self.qkv_w(p), qkv,
-                             norm=(self.w(p + "input_layernorm.weight"), d.rms_eps))
-                else:
-                    h = torch.empty_like(x)
-                    ops.rmsnorm(x, self.w(p + "input_layernorm.weight"), h, None, d.rms_eps)
-                    self.lin(h, p + "self_attn.q_proj.weight", self.qkv_w(p), qkv)
-                ops.qkv_rope_split(qkv, apos, self.rope(g.theta), Q, Kj, Vj, B, d.H, nh, 1, hd, d.H, 0, Lp, g.off)
-            if self.infer_flash and not isinstance(cnt, GeneralMask):  # fused attention over every cached key
-                if O is None:
-                    O = torch.empty(B * d.H, nh * hd, device=dev, dtype=BF16)
-                if self.decode_attn_ok():  # one workgroup per (head, sample), no key split / combine launch
-                    ops.decode_attn(Q, d.H, 0, Kj, Vj, O, B, nh, d.H, L, 1.0 / math.sqrt(hd), 50.0, cnt, d.P, d.C,
-                                    g.off)
-                else:
-                    ops.flash_fwd(self._attn_flash_infer(Q, Kj, Vj, [(g.off, d.H, O)], d.H, L, g.off, cnt, B))
-                x = self._post_attn_O(g, p, x, O)
-                continue
-            if S is None:
-                S = torch.empty(B, d.H * nh, Lp, device=dev, dtype=F32)
-                Pm = torch.empty(B, d.H * nh, Lp, device=dev, dtype=BF16)
-            ops.gemm(d.H * nh, L, hd, Q, hd, True, Kj, hd, True, S, Lp, batch=B, sA=(d.H * nh * hd, 0),
-                     sB=(Lp * hd, 0), sC=(d.H * nh * Lp, 0))
-            ops.attn_softmax(S, Lp, Pm, Lp, B * d.H * nh, L, 1.0 / math.sqrt(hd), cap=50.0,
-                             rows_per_batch=d.H * nh, heads=nh, qoff=d.P + d.C, **_mask_kw(d, cnt, "act"))
-            x = self._post_attn(g, p, x, Pm, Vj, B, d.H, Lp, qrow0=0)
+            self._qkv_infer(g, l, x, apos, Q, Kj, Vj, B, d.H, 0, g.off, "decode")
+            if not flash:
+                if S is None:
+                    S = torch.empty(B, d.H * nh, d.Lp, device=dev, dtype=F32)
+                self._attn_gemm(Q, Kj, Vj, S, {g.name: O}, [g], g.off, d.H, L, "act", cnt, B)
+            elif self.decode_attn_ok():  # one workgroup per (head, sample), no key split / combine launch
+                ops.decode_attn(Q, d.H, 0, Kj, Vj, O, B, nh, d.H, L, 1.0 / math.sqrt(hd), 50.0, cnt, d.P, d.C, g.off)
+            else:  # fused attention over every cached key
+                ops.flash_fwd(self._attn_flash_infer(Q, Kj, Vj, [(g.off, d.H, O)], d.H, L, g.off, cnt, B))
+            x = self._post_attn(g, l, x, O, plain=not flash)
         if glue:
             ops.action_out(x, self.w("joint_model.mixtures.action.norm.weight"), d.rms_eps,
                            self.w("action_decoder.weight"), self.w("action_decoder.bias"), action, t, B, d.H,
@@ -1990,44 +1881,28 @@ class Engine:
         (pizero.py:492-557): the proprio AND action rows of every sample run again with cond(t) -- the proprio K/V
         depend on t, so only the vlm K/V are cached -- under the block mask (proprio -> vlm + proprio, action ->
         all).  Unfused sites: adaptive norm launches, plain q|k|v GEMM + RoPE split, the flash kernel with the query
-        rows starting at token P (or GEMM + softmax), the adaptive final norm + decoder + Euler tail."""
+        rows starting at token P (or GEMM + softmax), the adaptive final norm + decoder + Euler tail.  Xp: the proprio
+        rows, already times sqrt(hidden)."""
         d = self.d
         dev = action.device
-        nh, hd, Lp, L = d.nh, d.hd, d.Lp, d.L
-        tied = self.m._tied
+        nh, hd, L = d.nh, d.hd, d.L
         T = d.C + d.H
         cond = torch.empty(B, d.tH, device=dev, dtype=BF16)
         ops.time_embed(t, cond, d.tmax, ref_bf16=d.time_bf16)
-        groups = self.groups(tied, active=("proprio", "action"))
+        groups = self.groups(self.m._tied, active=("proprio", "action"))
         ada = {g.name: Ada(self, g, cond) for g in groups}
         psi = torch.empty(B * d.H, d.A, device=dev, dtype=BF16)
         ops.cast_to_bf16(action, psi)
-        e3 = self.action_embed(psi, t, None)
-        sa = math.sqrt(d.aH)
-        if tied:
-            Xe = torch.empty(B * T, d.aH, device=dev, dtype=BF16)
-            ops.copy_rows(Xp, d.aH, d.C * d.aH, Xe, d.aH, T * d.aH, B, d.C, d.aH)
-            ops.copy_rows(e3, d.aH, d.H * d.aH, Xe[d.C:], d.aH, T * d.aH, B, d.H, d.aH, scale=sa)
-            X = {"expert": Xe}
-        else:
-            Xa = torch.empty(B * d.H, d.aH, device=dev, dtype=BF16)
-            ops.copy_rows(e3, d.aH, 0, Xa, d.aH, 0, 1, B * d.H, d.aH, scale=sa)
-            X = {"proprio": Xp, "action": Xa}
+        X = self._expert_rows(Xp, self.action_embed(psi, t, None), B, None)
         Q = torch.empty(B, T, nh * hd, device=dev, dtype=BF16)
-        S = Pm = None
+        S = None
         flash = self.infer_flash and not isinstance(cnt, GeneralMask)
         for l in range(d.nL):
             last = l == d.nL - 1
             Kj, Vj = kcache[l], vcache[l]
             for g in groups:
-                p = f"{g.prefix}{l}."
-                x = X[g.name]
-                h = torch.empty_like(x)
-                ada[g.name].norm_fwd(x, l, "in_", g.T, h)
-                qkv = torch.empty(x.shape[0], (nh + 2) * hd, device=dev, dtype=BF16)
-                ops.linear(h, self.qkv_w(p), qkv)
-                ops.qkv_rope_split(qkv, pos[g.pos_key], self.rope(g.theta), Q, Kj, Vj, B, g.T, nh, 1, hd, T, g.off - d.P,
-                                   Lp, g.off)
+                self._qkv_infer(g, l, X[g.name], pos[g.name], Q, Kj, Vj, B, T, g.off - d.P, g.off,
+                                "plain", A=ada[g.name])
             # (an untied proprio mixture's last-layer output feeds nothing: computed with the rest -- every query row
             # belongs to an output group -- and dropped)
             live = [g for g in groups if not (last and g.skip_last)]
@@ -2037,24 +1912,17 @@ class Engine:
                                                      cnt, B))
             else:
                 if S is None:
-                    S = torch.empty(B, T * nh, Lp, device=dev, dtype=F32)
-                    Pm = torch.empty(B, T * nh, Lp, device=dev, dtype=BF16)
-                ops.gemm(T * nh, L, hd, Q, hd, True, Kj, hd, True, S, Lp, batch=B, sA=(T * nh * hd, 0),
-                         sB=(Lp * hd, 0), sC=(T * nh * Lp, 0))
-                ops.attn_softmax(S, Lp, Pm, Lp, B * T * nh, L, 1.0 / math.sqrt(hd), cap=50.0, rows_per_batch=T * nh,
-                                 heads=nh, qoff=d.P, **_mask_kw(d, cnt, "act"))
-                for g in live:
-                    ops.gemm(g.T * nh, hd, Lp, Pm[:, (g.off - d.P) * nh:], Lp, True, Vj, hd, False, Os[g.name], hd,
-                             batch=B, sA=(T * nh * Lp, 0), sB=(Lp * hd, 0), sC=(g.T * nh * hd, 0))
+                    S = torch.empty(B, T * nh, d.Lp, device=dev, dtype=F32)
+                self._attn_gemm(Q, Kj, Vj, S, Os, live, d.P, T, L, "act", cnt, B)
             for g in live:
-                self._post_attn_ada(ada[g.name], g, l, X, None, Os, dev, keep=False)
-        ag = "expert" if tied else "action"
-        Tg, aoff = (T, d.C) if tied else (d.H, 0)
-        y = torch.empty_like(X[ag])
-        ada[ag].norm_fwd(X[ag], "norm", "", Tg, y)
-        v = torch.empty(B * Tg, 8, device=dev, dtype=BF16)
+                X[g.name] = self._post_attn(g, l, X[g.name], Os[g.name], ada[g.name])
+        ga = groups[-1]  # the group that holds the action rows: the tied group's follow its proprio rows
+        aoff = ga.T - d.H
+        y = torch.empty_like(X[ga.name])
+        self._norm_fwd(ada[ga.name], ga, X[ga.name], "norm", "", y)
+        v = torch.empty(B * ga.T, 8, device=dev, dtype=BF16)
         ops.small_linear(y, self.w("action_decoder.weight"), v[:, : d.A], bias=self.w("action_decoder.bias"))
-        ops.euler_step(action, v[aoff:], 8, Tg * 8, t, B, d.H, d.A, 1.0 / d.steps)
+        ops.euler_step(action, v[aoff:], 8, ga.T * 8, t, B, d.H, d.A, 1.0 / d.steps)
 
     @_merged_weights
     def infer_action(self, ids, pix, cnt, vpos, ppos, apos, proprios, noise, kcache, vcache, clip=True):
@@ -2064,9 +1932,9 @@ class Engine:
         cannot work, since the proprio K/V depend on t."""
         d = self.d
         B = ids.shape[0]
+        dev = pix.device
         self.fp8_refresh()
         if d.ada:
-            dev = pix.device
             self.prefill(ids, pix, cnt, vpos, None, None, kcache, vcache, with_proprio=False)
             Xp = self._proprio_rows(proprios, B, dev)
             if self.m._tied:
@@ -2078,18 +1946,14 @@ class Engine:
                 m[:, : d.C, : d.P + d.C] = cnt.itp[:, d.P:, :]
                 m[:, d.C:, :] = cnt.act
                 cnt = GeneralMask(itp=cnt.itp, act=m)
-            action = noise.clone()
-            t = torch.zeros(B, device=dev, dtype=F32)
-            for _ in range(d.steps):
-                self.denoise_step_ada(action, t, Xp, pos, cnt, kcache, vcache, B)
-            if clip and d.clip is not None:
-                ops.clamp_(action, -d.clip, d.clip)
-            return action
-        self.prefill(ids, pix, cnt, vpos, ppos, proprios, kcache, vcache)
+            step = functools.partial(self.denoise_step_ada, Xp=Xp, pos=pos)
+        else:
+            self.prefill(ids, pix, cnt, vpos, ppos, proprios, kcache, vcache)
+            step = functools.partial(self.denoise_step, apos=apos)
         action = noise.clone()
-        t = torch.zeros(B, device=pix.device, dtype=F32)
+        t = torch.zeros(B, device=dev, dtype=F32)
         for _ in range(d.steps):
-            self.denoise_step(action, t, apos, cnt, kcache, vcache, B)
+            step(action, t, cnt=cnt, kcache=kcache, vcache=vcache, B=B)
         if clip and d.clip is not None:
             ops.clamp_(action, -d.clip, d.clip)
         return action
