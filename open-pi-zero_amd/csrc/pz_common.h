@@ -130,6 +130,20 @@ void pz_set_error(const char* fmt, ...);
   } while (0)
 #define PZ_ALIGNED(p, n) ((((uintptr_t)(p)) % (n)) == 0)
 
+// compute units of the current device (grids of one workgroup per CU: the 8-phase GEMM's wave of resident
+// workgroups, the persistent SigLIP attention kernels); 256 when the runtime cannot say
+static inline int pz_device_cus() {
+  static int cache[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (!cache[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cache[dev] = n;
+  }
+  return cache[dev];
+}
+
 // RoPE rotation of one pair (utils.py:4-16: x*cos + rotate_half(x)*sin) with every product rounded
 // separately (no FMA contraction): every kernel that applies RoPE (qkv_rope_split, the GEMV and the 8-phase
 // GEMM epilogues) produces the same bits from the same bf16 inputs

@@ -19,6 +19,16 @@
 // The backward mirrors it with S = Q K^T (key on the lane), so dV^T = dO^T P and dK^T = Q^T dS take
 // P / dS from registers and dO^T / Q^T through transposed LDS reads; dQ = dS K is a separate
 // query-parallel pass (no atomics: deterministic).
+//
+// Shared pieces (general = step-staged, any head dim; res = resident, 2 / 4 workgroups per unit; unit = one
+// workgroup per unit):
+//   FaResKV   the unit's resident K + V images: flash_fwd_res / flash_fwd_unit / flash_bwd_q_res / flash_bwd_q_unit
+//   FaDqRows  dQ row prologue (Q / dO fragments, delta, lse) and dQ store: flash_bwd_q2 and, through FaDq, the two below
+//   FaDq      dQ block step over the resident images: flash_bwd_q_res (<72, 1, false>), flash_bwd_q_unit (<72, 2, PLAIN>)
+//   fa_store_row  the bf16 O / dQ / dK / dV row store of all nine kernels
+// The forward block steps and the dK/dV kernels stay written out per form: on shared steps they cost registers or
+// time (profiles/flash_share/isa_compare.txt, timing.txt).  The *_sig, probs / ds DMA, fp8, combine, reduce and
+// prep kernels share nothing with these.
 #include "pz_common.h"
 
 #include <type_traits>
@@ -28,6 +38,7 @@ namespace {
 constexpr int FA_KB = 64;   // keys per staged block (forward, dQ) / per dK-dV workgroup
 constexpr int FA_NW = 4;    // waves per workgroup (backward)
 constexpr int FA_QS = 32;   // query rows per staged step of the dK/dV pass
+constexpr float FA_LOG2E = 1.4426950408889634f, FA_LN2 = 0.6931471805599453f;
 
 template <int HD>
 struct FaDims {
@@ -125,6 +136,11 @@ __device__ __forceinline__ void zero_pad_cols(bf16_t* T) {
   }
 }
 
+struct FaUnit {  // attention unit zh = b * H + h: sample (or sample x mixture) b, head h
+  int64_t zh, b, h;
+  __device__ __forceinline__ FaUnit(const pz_flash_args& a, int64_t zh_) : zh(zh_), b(zh_ / a.H), h(zh_ % a.H) {}
+};
+
 struct FaRow {  // where O / dO row r of unit (b, h) lives
   const pz_flash_args* a;
   __device__ __forceinline__ int grp(int64_t r) const {
@@ -215,6 +231,19 @@ __device__ __forceinline__ float fa_logit(const FaMask& mk, float s, int t, int 
 }
 
 // ------------------------------------------------------------------ forward --
+// store 4 consecutive head dims per 16-wide block of row `dst` (lane group g owns dims 16 db + 4g ..), scaled by f:
+// the bf16 O / dQ / dK / dV row store of every forward and backward kernel up to the one-workgroup-per-unit ones
+template <int HD, int NB>
+__device__ __forceinline__ void fa_store_row(bf16_t* dst, const f32x4 (&x)[FaDims<HD>::NDB][NB], int blk, int g, float f) {
+#pragma unroll
+  for (int db = 0; db < FaDims<HD>::NDB; ++db) {
+    const int d = db * 16 + 4 * g;
+    if (d < HD)
+      *reinterpret_cast<u32x2*>(dst + d) =
+          u32x2{pack2bf(x[db][blk][0] * f, x[db][blk][1] * f), pack2bf(x[db][blk][2] * f, x[db][blk][3] * f)};
+  }
+}
+
 // grid (ceil(nq / 128), Z * H), FNW waves: wave w owns query rows q0 + 16*FNQB*w .. + 16*FNQB - 1
 template <int HD>
 __global__ void __launch_bounds__(FaDims<HD>::FNW * 64) flash_fwd_kernel(pz_flash_args a) {
@@ -373,14 +402,7 @@ __global__ void __launch_bounds__(FaDims<HD>::FNW * 64) flash_fwd_kernel(pz_flas
     if (r >= a.nq) continue;
     const float inv = l[qb] > 0.f ? 1.f / l[qb] : 0.f;
     const int gi = fr.grp(r);
-    bf16_t* O = (bf16_t*)a.g_o[gi] + fr.off(b, h, r, gi);
-#pragma unroll
-    for (int db = 0; db < D::NDB; ++db) {
-      const int d = db * 16 + 4 * g;
-      if (d < HD)
-        *reinterpret_cast<u32x2*>(O + d) =
-            u32x2{pack2bf(o[db][qb][0] * inv, o[db][qb][1] * inv), pack2bf(o[db][qb][2] * inv, o[db][qb][3] * inv)};
-    }
+    fa_store_row<HD>((bf16_t*)a.g_o[gi] + fr.off(b, h, r, gi), o, qb, g, inv);
     if (g == 0 && a.lse) a.lse[zh * a.nq + r] = m[qb] + __logf(l[qb]);
   }
 }
@@ -496,6 +518,133 @@ struct FaFast {
   }
 };
 
+// ---- shared pieces of the backward kernels ---------------------------------------------------
+// dQ row prologue of one wave: NQB 16-row query blocks starting at row r0; Q / dO fragments (B operands: k = head
+// dim, n = query) straight from HBM, delta = rowsum(dO . O) (written out for the dK/dV pass), lse
+template <int HD, int NQB>
+struct FaDqRows {
+  using D = FaDims<HD>;
+  bf16x8 qf[NQB][D::NKS], df[NQB][D::NKS];
+  float del[NQB], lse[NQB];
+  int tq[NQB];
+  bool live[NQB];
+  int r0;  // first query row (nq < 2^22, host-checked)
+  __device__ __forceinline__ void load(const pz_flash_args& a, const FaMask& mk, const bf16_t* Q, const FaUnit& u,
+                                       int r0_, int lane) {
+    const FaRow fr{&a};
+    const int g = lane >> 4;
+    r0 = r0_;
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+      const int64_t r = r0 + qb * 16 + (lane & 15);
+      live[qb] = r < a.nq;
+      tq[qb] = mk.token((int)r);
+      const bf16_t* dOr = nullptr;
+      const bf16_t* Or = nullptr;
+      if (live[qb]) {
+        const int gi = fr.grp(r);
+        dOr = (const bf16_t*)a.g_do[gi] + fr.off(u.b, u.h, r, gi);
+        Or = (const bf16_t*)a.g_o[gi] + fr.off(u.b, u.h, r, gi);
+      }
+      float dl = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < D::NKS; ++ks) {
+        const int c = ks * 32 + 8 * g;
+        const bool ok = live[qb] && c < HD;
+        qf[qb][ks] = ok ? *reinterpret_cast<const bf16x8*>(Q + r * a.ldq + c) : bf16x8{};
+        df[qb][ks] = ok ? *reinterpret_cast<const bf16x8*>(dOr + c) : bf16x8{};
+        if (ok) {
+          const bf16x8 ov = *reinterpret_cast<const bf16x8*>(Or + c);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) dl += (float)df[qb][ks][e] * (float)ov[e];
+        }
+      }
+      dl += __shfl_xor(dl, 16, 64);
+      dl += __shfl_xor(dl, 32, 64);
+      del[qb] = dl;
+      if (live[qb] && g == 0) a.delta[u.zh * a.nq + r] = dl;
+      lse[qb] = live[qb] ? a.lse[u.zh * a.nq + r] : 0.f;
+    }
+  }
+  // dQ[r][d..d+3] = f dQ^T
+  __device__ __forceinline__ void store(const pz_flash_args& a, const FaUnit& u, int lane,
+                                        const f32x4 (&dq)[D::NDB][NQB], float f) const {
+    bf16_t* dQ = (bf16_t*)a.dq + u.b * a.q_bstride + u.h * a.q_hstride;
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb)
+      if (live[qb]) fa_store_row<HD>(dQ + (int64_t)(r0 + qb * 16 + (lane & 15)) * a.ldq, dq, qb, lane >> 4, f);
+  }
+};
+
+// dQ of the resident kernels: the rows above swept over the unit's 64-key blocks (K / V images in LDS).
+// PLAIN: log2-domain P, dS without the scale (applied to dQ once, in the epilogue); keys past nk are zero rows
+// of the K / V images: no contribution
+template <int HD, int NQB, bool PLAIN>
+struct FaDq : FaDqRows<HD, NQB> {
+  using D = FaDims<HD>;
+  f32x4 dq[D::NDB][NQB];
+  float sl2;
+  __device__ __forceinline__ void init(const pz_flash_args& a, const FaMask& mk, const bf16_t* Q, const FaUnit& u,
+                                       int r0_, int lane) {
+    this->load(a, mk, Q, u, r0_, lane);
+    sl2 = a.scale * FA_LOG2E;
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+      if constexpr (PLAIN) this->lse[qb] *= FA_LOG2E;
+#pragma unroll
+      for (int db = 0; db < D::NDB; ++db) dq[db][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  __device__ __forceinline__ void step(const FaMask& mk, const bf16_t* Ks, const bf16_t* Vs, int kb, int lane) {
+    const int g = lane >> 4;
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {  // 32 keys at a time
+      f32x4 ds[2][NQB];  // dS^T[key 32 k2 + 16 ii + 4g + e][query of block qb]
+#pragma unroll
+      for (int ii = 0; ii < 2; ++ii) {
+        const int i = 2 * k2 + ii;
+        bf16x8 kfr[D::NKS], vfr[D::NKS];
+#pragma unroll
+        for (int ks = 0; ks < D::NKS; ++ks) {
+          kfr[ks] = frag_row<D::ROW>(Ks, i * 16, ks * 32, lane);
+          vfr[ks] = frag_row<D::ROW>(Vs, i * 16, ks * 32, lane);
+        }
+#pragma unroll
+        for (int qb = 0; qb < NQB; ++qb) {
+          f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ks = 0; ks < D::NKS; ++ks) {
+            sv = mfma(kfr[ks], this->qf[qb][ks], sv);
+            dp = mfma(vfr[ks], this->df[qb][ks], dp);
+          }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int j = kb * FA_KB + i * 16 + 4 * g + e;
+            float dse = 0.f;
+            if constexpr (PLAIN) {
+              dse = __builtin_amdgcn_exp2f(sv[e] * sl2 - this->lse[qb]) * (dp[e] - this->del[qb]);
+            } else if (this->live[qb]) {
+              const FaLogit lg = fa_logit_d(mk, sv[e], this->tq[qb], j);
+              const float pe = lg.x == -INFINITY ? 0.f : __expf(lg.x - this->lse[qb]);
+              dse = pe * (dp[e] - this->del[qb]) * lg.dxds;
+            }
+            ds[ii][qb][e] = dse;
+          }
+        }
+      }
+      bf16x8 sb[NQB];
+#pragma unroll
+      for (int qb = 0; qb < NQB; ++qb) sb[qb] = pack8(ds[0][qb], ds[1][qb]);
+#pragma unroll
+      for (int db = 0; db < D::NDB; ++db) {
+        const bf16x8 kt = frag_tr<D::ROW>(Ks, k2 * 32, db * 16, lane);
+#pragma unroll
+        for (int qb = 0; qb < NQB; ++qb) dq[db][qb] = mfma(kt, sb[qb], dq[db][qb]);
+      }
+    }
+  }
+};
+
 // delta[z][r] = sum_d dO[r][d] O[r][d]: one wave per row
 template <int HD>
 __global__ void __launch_bounds__(256) flash_bwd_prep_kernel(pz_flash_args a) {
@@ -589,9 +738,9 @@ __global__ void __launch_bounds__(FA_NW * 64, HD == 256 ? 1 : 2) flash_bwd_kv_ke
     sk.load(V, a.ldv, k0, a.nk);
     sk.store(Vk);
   }
-  f32x4 dk[D::NDB], dv[D::NDB];
+  f32x4 dk[D::NDB][1], dv[D::NDB][1];
 #pragma unroll
-  for (int db = 0; db < D::NDB; ++db) dk[db] = dv[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int db = 0; db < D::NDB; ++db) dk[db][0] = dv[db][0] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   __syncthreads();  // pad columns zeroed
   stq.store(Qs2[0]);
@@ -669,8 +818,8 @@ __global__ void __launch_bounds__(FA_NW * 64, HD == 256 ? 1 : 2) flash_bwd_kv_ke
       for (int x = 0; x < HB; ++x) {
         const int db = hb * HB + x;
         if (db < D::NDB) {
-          dv[db] = mfma(dt[x], pb, dv[db]);
-          dk[db] = mfma(qt[x], sb, dk[db]);
+          dv[db][0] = mfma(dt[x], pb, dv[db][0]);
+          dk[db][0] = mfma(qt[x], sb, dk[db][0]);
         }
       }
     }
@@ -688,7 +837,7 @@ __global__ void __launch_bounds__(FA_NW * 64, HD == 256 ? 1 : 2) flash_bwd_kv_ke
   }
   if (key >= a.nk) return;
 #pragma unroll
-  for (int db = 0; db < D::NDB; ++db) dk[db] *= ff.scale;  // the fast path's dS' excludes the softmax scale
+  for (int db = 0; db < D::NDB; ++db) dk[db][0] *= ff.scale;  // the fast path's dS' excludes the softmax scale
   if (splits > 1) {  // fp32 partial sums of this query split -> ws[split][unit][key][HD] (dK), then dV
     const int64_t slab = ZH * a.nk * HD;
     float* pk = a.ws + ((int64_t)split * ZH + zh) * a.nk * HD + (int64_t)key * HD;
@@ -697,22 +846,16 @@ __global__ void __launch_bounds__(FA_NW * 64, HD == 256 ? 1 : 2) flash_bwd_kv_ke
     for (int db = 0; db < D::NDB; ++db) {
       const int d = db * 16 + 4 * g;
       if (d < HD) {
-        *reinterpret_cast<f32x4*>(pk + d) = dk[db];
-        *reinterpret_cast<f32x4*>(pv + d) = dv[db];
+        *reinterpret_cast<f32x4*>(pk + d) = dk[db][0];
+        *reinterpret_cast<f32x4*>(pv + d) = dv[db][0];
       }
     }
     return;
   }
   bf16_t* dK = (bf16_t*)a.dk + b * a.k_bstride + h * a.k_hstride + (int64_t)key * a.ldk;
   bf16_t* dV = (bf16_t*)a.dv + b * a.v_bstride + h * a.v_hstride + (int64_t)key * a.ldv;
-#pragma unroll
-  for (int db = 0; db < D::NDB; ++db) {
-    const int d = db * 16 + 4 * g;
-    if (d < HD) {
-      *reinterpret_cast<u32x2*>(dK + d) = u32x2{pack2bf(dk[db][0], dk[db][1]), pack2bf(dk[db][2], dk[db][3])};
-      *reinterpret_cast<u32x2*>(dV + d) = u32x2{pack2bf(dv[db][0], dv[db][1]), pack2bf(dv[db][2], dv[db][3])};
-    }
-  }
+  fa_store_row<HD>(dK, dk, 0, g, 1.f);
+  fa_store_row<HD>(dV, dv, 0, g, 1.f);
 }
 
 // sum of the query-split partials (fixed order) -> bf16 dK / dV; one thread per 4 elements
@@ -747,13 +890,13 @@ __global__ void __launch_bounds__(JQ_NW * 64, 1) flash_bwd_q2_kernel(pz_flash_ar
   int64_t zh;
   int qblk;
   fa_unit_block((int)((a.nq + RPW - 1) / RPW), (int)(a.Z * a.H), zh, qblk);
-  const int64_t b = zh / a.H, h = zh % a.H;
+  const FaUnit u(a, zh);
+  const int64_t b = u.b, h = u.h;
   const bf16_t* Q = (const bf16_t*)a.q + b * a.q_bstride + h * a.q_hstride;
   const bf16_t* K = (const bf16_t*)a.k + b * a.k_bstride + h * a.k_hstride;
   const bf16_t* V = (const bf16_t*)a.v + b * a.v_bstride + h * a.v_hstride;
   const FaMask mk(a, b);
   const FaFast ff(a);
-  const FaRow fr{&a};
 #pragma unroll
   for (int bi = 0; bi < 2; ++bi) {
     zero_pad_cols<HD, D::HDK, D::ROW, JQ_KB, NT>(Ks2[bi]);
@@ -764,41 +907,15 @@ __global__ void __launch_bounds__(JQ_NW * 64, 1) flash_bwd_q2_kernel(pz_flash_ar
   TileStager<HD, D::ROW, JQ_KB, NT> stk, stv;
   stk.load(K, a.ldk, 0, a.nk);
   stv.load(V, a.ldv, 0, a.nk);
-  bf16x8 qf[2][D::NKS], df[2][D::NKS];
-  float del[2], lse2[2], crow[2];
+  FaDqRows<HD, 2> rw;
+  rw.load(a, mk, Q, u, qblk * RPW + wave * 32, lane);
+  float lse2[2], crow[2];
   int rb[2];
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) {
-    const int64_t r = (int64_t)qblk * RPW + wave * 32 + qb * 16 + (lane & 15);
-    const bool live = r < a.nq;
-    const bf16_t* dOr = nullptr;
-    const bf16_t* Or = nullptr;
-    if (live) {
-      const int gi = fr.grp(r);
-      dOr = (const bf16_t*)a.g_do[gi] + fr.off(b, h, r, gi);
-      Or = (const bf16_t*)a.g_o[gi] + fr.off(b, h, r, gi);
-    }
-    float dl = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < D::NKS; ++ks) {
-      const int c = ks * 32 + 8 * g;
-      const bool ok = live && c < HD;
-      qf[qb][ks] = ok ? *reinterpret_cast<const bf16x8*>(Q + r * a.ldq + c) : bf16x8{};
-      df[qb][ks] = ok ? *reinterpret_cast<const bf16x8*>(dOr + c) : bf16x8{};
-      if (ok) {
-        const bf16x8 ov = *reinterpret_cast<const bf16x8*>(Or + c);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dl += (float)df[qb][ks][e] * (float)ov[e];
-      }
-    }
-    dl += __shfl_xor(dl, 16, 64);
-    dl += __shfl_xor(dl, 32, 64);
-    del[qb] = dl;
-    if (live && g == 0) a.delta[zh * a.nq + r] = dl;
-    lse2[qb] = live ? a.lse[zh * a.nq + r] * 1.4426950408889634f : 0.f;
-    const int t = mk.token((int)r);
-    rb[qb] = fa_row_bits(mk, t);
-    crow[qb] = mk.dead(t) ? 0.f : ff.crow_live;
+    lse2[qb] = rw.lse[qb] * FA_LOG2E;
+    rb[qb] = fa_row_bits(mk, rw.tq[qb]);
+    crow[qb] = mk.dead(rw.tq[qb]) ? 0.f : ff.crow_live;
   }
   f32x4 dq[D::NDB][2];
 #pragma unroll
@@ -831,14 +948,14 @@ __global__ void __launch_bounds__(JQ_NW * 64, 1) flash_bwd_q2_kernel(pz_flash_ar
         f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < D::NKS; ++ks) {
-          sv = mfma(kfr[ks], qf[qb][ks], sv);
-          dp = mfma(vfr[ks], df[qb][ks], dp);
+          sv = mfma(kfr[ks], rw.qf[qb][ks], sv);
+          dp = mfma(vfr[ks], rw.df[qb][ks], dp);
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const bool ok = full || ((rb[qb] >> fa_key_class(mk, kb * JQ_KB + i * 16 + 4 * g + e)) & 1);
           float pe, dse;
-          ff.eval<CAP>(sv[e], dp[e], lse2[qb], crow[qb], del[qb], ok, pe, dse);
+          ff.eval<CAP>(sv[e], dp[e], lse2[qb], crow[qb], rw.del[qb], ok, pe, dse);
           ds[i][qb][e] = dse;
         }
       }
@@ -866,19 +983,7 @@ __global__ void __launch_bounds__(JQ_NW * 64, 1) flash_bwd_q2_kernel(pz_flash_ar
     }
     __syncthreads();
   }
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int64_t r = (int64_t)qblk * RPW + wave * 32 + qb * 16 + (lane & 15);
-    if (r >= a.nq) continue;
-    bf16_t* dQ = (bf16_t*)a.dq + b * a.q_bstride + h * a.q_hstride + r * a.ldq;
-#pragma unroll
-    for (int db = 0; db < D::NDB; ++db) {
-      const int d = db * 16 + 4 * g;
-      if (d < HD)
-        *reinterpret_cast<u32x2*>(dQ + d) = u32x2{pack2bf(dq[db][qb][0] * ff.scale, dq[db][qb][1] * ff.scale),
-                                                  pack2bf(dq[db][qb][2] * ff.scale, dq[db][qb][3] * ff.scale)};
-    }
-  }
+  rw.store(a, u, lane, dq, ff.scale);
 }
 
 // ---- joint attention with the softmax probabilities exported (training default): see flash_fwd_probs_dma_kernel
@@ -891,24 +996,19 @@ constexpr int JP_NW = 8, JP_MAXKB = 5;
 // work (16 heads x 72).  8 waves per workgroup (two per SIMD), dynamic LDS up to 142 KiB.
 constexpr int FR_MAX = 256, FR_NW = 8;
 
+// the unit's K / V base pointers and its resident K + V images (forward, dQ), staged by all 512 threads at once
 template <int HD>
-__global__ void __launch_bounds__(FR_NW * 64) flash_fwd_res_kernel(pz_flash_args a) {
+struct FaResKV {
   using D = FaDims<HD>;
-  constexpr int NT = FR_NW * 64;
-  extern __shared__ __attribute__((aligned(16))) char fa_smem[];
-  bf16_t* Kall = reinterpret_cast<bf16_t*>(fa_smem);
-  bf16_t* Vall = Kall + FR_MAX * D::ROW;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
-  int64_t zh;
-  int qblk;
-  fa_unit_block((int)((a.nq + FR_NW * 16 - 1) / (FR_NW * 16)), (int)(a.Z * a.H), zh, qblk);
-  const int64_t b = zh / a.H, h = zh % a.H;
-  const int64_t q0 = (int64_t)qblk * (FR_NW * 16) + wave * 16;
-  const bf16_t* Q = (const bf16_t*)a.q + b * a.q_bstride + h * a.q_hstride;
-  const bf16_t* K = (const bf16_t*)a.k + b * a.k_bstride + h * a.k_hstride;
-  const bf16_t* V = (const bf16_t*)a.v + b * a.v_bstride + h * a.v_hstride;
-  const FaMask mk(a, b);
-  {
+  const bf16_t *Q, *K, *V;
+  bf16_t *Kall, *Vall;
+  __device__ __forceinline__ FaResKV(const pz_flash_args& a, const FaUnit& u, char* smem) {
+    Q = (const bf16_t*)a.q + u.b * a.q_bstride + u.h * a.q_hstride;
+    K = (const bf16_t*)a.k + u.b * a.k_bstride + u.h * a.k_hstride;
+    V = (const bf16_t*)a.v + u.b * a.v_bstride + u.h * a.v_hstride;
+    Kall = reinterpret_cast<bf16_t*>(smem);
+    Vall = Kall + FR_MAX * D::ROW;
+    constexpr int NT = FR_NW * 64;
     TileStager<HD, D::ROW, FR_MAX, NT> stk, stv;
     stk.load(K, a.ldk, 0, a.nk);
     stv.load(V, a.ldv, 0, a.nk);
@@ -917,6 +1017,23 @@ __global__ void __launch_bounds__(FR_NW * 64) flash_fwd_res_kernel(pz_flash_args
     stk.store(Kall);
     stv.store(Vall);
   }
+  __device__ __forceinline__ const bf16_t* ks(int kb) const { return Kall + kb * FA_KB * D::ROW; }
+  __device__ __forceinline__ const bf16_t* vs(int kb) const { return Vall + kb * FA_KB * D::ROW; }
+};
+
+template <int HD>
+__global__ void __launch_bounds__(FR_NW * 64) flash_fwd_res_kernel(pz_flash_args a) {
+  using D = FaDims<HD>;
+  extern __shared__ __attribute__((aligned(16))) char fa_smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  int64_t zh;
+  int qblk;
+  fa_unit_block((int)((a.nq + FR_NW * 16 - 1) / (FR_NW * 16)), (int)(a.Z * a.H), zh, qblk);
+  const int64_t b = zh / a.H, h = zh % a.H;
+  const int64_t q0 = (int64_t)qblk * (FR_NW * 16) + wave * 16;
+  const FaMask mk(a, b);
+  const FaResKV<HD> kv(a, FaUnit(a, zh), fa_smem);
+  const bf16_t* Q = kv.Q;
   bf16x8 qf[D::NKS];
   const int64_t rq = q0 + (lane & 15);
 #pragma unroll
@@ -924,16 +1041,16 @@ __global__ void __launch_bounds__(FR_NW * 64) flash_fwd_res_kernel(pz_flash_args
     const int c = ks * 32 + 8 * g;
     qf[ks] = (rq < a.nq && c < HD) ? *reinterpret_cast<const bf16x8*>(Q + rq * a.ldq + c) : bf16x8{};
   }
-  f32x4 o[D::NDB];
+  f32x4 o[D::NDB][1];
 #pragma unroll
-  for (int db = 0; db < D::NDB; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int db = 0; db < D::NDB; ++db) o[db][0] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
   const int t = mk.token((int)rq);
   const int nkb = (int)((a.nk + FA_KB - 1) / FA_KB);
   __syncthreads();
   for (int kb = 0; kb < nkb; ++kb) {
-    const bf16_t* Ks = Kall + kb * FA_KB * D::ROW;
-    const bf16_t* Vs = Vall + kb * FA_KB * D::ROW;
+    const bf16_t* Ks = kv.ks(kb);
+    const bf16_t* Vs = kv.vs(kb);
     f32x4 sc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) sc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -968,136 +1085,39 @@ __global__ void __launch_bounds__(FR_NW * 64) flash_fwd_res_kernel(pz_flash_args
     l = l * alpha + sum;
     m = mn;
 #pragma unroll
-    for (int db = 0; db < D::NDB; ++db) o[db] *= alpha;
+    for (int db = 0; db < D::NDB; ++db) o[db][0] *= alpha;
     const bf16x8 pf0 = pack8(sc[0], sc[1]), pf1 = pack8(sc[2], sc[3]);
 #pragma unroll
     for (int db = 0; db < D::NDB; ++db) {
-      o[db] = mfma(frag_tr<D::ROW>(Vs, 0, db * 16, lane), pf0, o[db]);
-      o[db] = mfma(frag_tr<D::ROW>(Vs, 32, db * 16, lane), pf1, o[db]);
+      o[db][0] = mfma(frag_tr<D::ROW>(Vs, 0, db * 16, lane), pf0, o[db][0]);
+      o[db][0] = mfma(frag_tr<D::ROW>(Vs, 32, db * 16, lane), pf1, o[db][0]);
     }
   }
   if (rq >= a.nq) return;
   const float inv = l > 0.f ? 1.f / l : 0.f;
   const FaRow fr{&a};
   const int gi = fr.grp(rq);
-  bf16_t* O = (bf16_t*)a.g_o[gi] + fr.off(b, h, rq, gi);
-#pragma unroll
-  for (int db = 0; db < D::NDB; ++db) {
-    const int d = db * 16 + 4 * g;
-    if (d < HD)
-      *reinterpret_cast<u32x2*>(O + d) =
-          u32x2{pack2bf(o[db][0] * inv, o[db][1] * inv), pack2bf(o[db][2] * inv, o[db][3] * inv)};
-  }
+  fa_store_row<HD>((bf16_t*)a.g_o[gi] + fr.off(b, h, rq, gi), o, 0, g, inv);
   if (g == 0 && a.lse) a.lse[zh * a.nq + rq] = m + __logf(l);
 }
 
 // dQ (+ delta) with every key / value of the unit resident: grid (ceil(nq / 128), Z * H)
 template <int HD>
 __global__ void __launch_bounds__(FR_NW * 64) flash_bwd_q_res_kernel(pz_flash_args a) {
-  using D = FaDims<HD>;
-  constexpr int NT = FR_NW * 64;
   extern __shared__ __attribute__((aligned(16))) char fa_smem[];
-  bf16_t* Kall = reinterpret_cast<bf16_t*>(fa_smem);
-  bf16_t* Vall = Kall + FR_MAX * D::ROW;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int64_t zh;
   int qblk;
   fa_unit_block((int)((a.nq + FR_NW * 16 - 1) / (FR_NW * 16)), (int)(a.Z * a.H), zh, qblk);
-  const int64_t b = zh / a.H, h = zh % a.H;
-  const int64_t r = (int64_t)qblk * (FR_NW * 16) + wave * 16 + (lane & 15);
-  const bf16_t* Q = (const bf16_t*)a.q + b * a.q_bstride + h * a.q_hstride;
-  const bf16_t* K = (const bf16_t*)a.k + b * a.k_bstride + h * a.k_hstride;
-  const bf16_t* V = (const bf16_t*)a.v + b * a.v_bstride + h * a.v_hstride;
-  const FaMask mk(a, b);
-  const FaRow fr{&a};
-  {
-    TileStager<HD, D::ROW, FR_MAX, NT> stk, stv;
-    stk.load(K, a.ldk, 0, a.nk);
-    stv.load(V, a.ldv, 0, a.nk);
-    zero_pad_cols<HD, D::HDK, D::ROW, FR_MAX, NT>(Kall);
-    zero_pad_cols<HD, D::HDK, D::ROW, FR_MAX, NT>(Vall);
-    stk.store(Kall);
-    stv.store(Vall);
-  }
-  bf16x8 qf[D::NKS], df[D::NKS];
-  const bool live = r < a.nq;
-  const bf16_t* dOr = nullptr;
-  const bf16_t* Or = nullptr;
-  if (live) {
-    const int gi = fr.grp(r);
-    dOr = (const bf16_t*)a.g_do[gi] + fr.off(b, h, r, gi);
-    Or = (const bf16_t*)a.g_o[gi] + fr.off(b, h, r, gi);
-  }
-  float del = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < D::NKS; ++ks) {
-    const int c = ks * 32 + 8 * g;
-    const bool ok = live && c < HD;
-    qf[ks] = ok ? *reinterpret_cast<const bf16x8*>(Q + r * a.ldq + c) : bf16x8{};
-    df[ks] = ok ? *reinterpret_cast<const bf16x8*>(dOr + c) : bf16x8{};
-    if (ok) {
-      const bf16x8 ov = *reinterpret_cast<const bf16x8*>(Or + c);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) del += (float)df[ks][e] * (float)ov[e];
-    }
-  }
-  del += __shfl_xor(del, 16, 64);
-  del += __shfl_xor(del, 32, 64);
-  if (live && g == 0) a.delta[zh * a.nq + r] = del;
-  const float lse = live ? a.lse[zh * a.nq + r] : 0.f;
-  const int tq = mk.token((int)r);
-  f32x4 dq[D::NDB];
-#pragma unroll
-  for (int db = 0; db < D::NDB; ++db) dq[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const FaUnit u(a, zh);
+  const FaMask mk(a, u.b);
+  const FaResKV<HD> kv(a, u, fa_smem);
+  FaDq<HD, 1, false> q;
+  q.init(a, mk, kv.Q, u, qblk * (FR_NW * 16) + wave * 16, lane);
   const int nkb = (int)((a.nk + FA_KB - 1) / FA_KB);
   __syncthreads();
-  for (int kb = 0; kb < nkb; ++kb) {
-    const bf16_t* Ks = Kall + kb * FA_KB * D::ROW;
-    const bf16_t* Vs = Vall + kb * FA_KB * D::ROW;
-    f32x4 ds[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-      bf16x8 kfr[D::NKS], vfr[D::NKS];
-#pragma unroll
-      for (int ks = 0; ks < D::NKS; ++ks) {
-        kfr[ks] = frag_row<D::ROW>(Ks, i * 16, ks * 32, lane);
-        vfr[ks] = frag_row<D::ROW>(Vs, i * 16, ks * 32, lane);
-      }
-#pragma unroll
-      for (int ks = 0; ks < D::NKS; ++ks) {
-        sv = mfma(kfr[ks], qf[ks], sv);
-        dp = mfma(vfr[ks], df[ks], dp);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int j = kb * FA_KB + i * 16 + 4 * g + e;
-        float dse = 0.f;
-        if (live) {
-          const FaLogit lg = fa_logit_d(mk, sv[e], tq, j);
-          const float pe = lg.x == -INFINITY ? 0.f : __expf(lg.x - lse);
-          dse = pe * (dp[e] - del) * lg.dxds;
-        }
-        ds[i][e] = dse;
-      }
-    }
-#pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {
-      const bf16x8 sb = pack8(ds[2 * k2], ds[2 * k2 + 1]);
-      bf16x8 kt[D::NDB];
-#pragma unroll
-      for (int db = 0; db < D::NDB; ++db) kt[db] = frag_tr<D::ROW>(Ks, k2 * 32, db * 16, lane);
-#pragma unroll
-      for (int db = 0; db < D::NDB; ++db) dq[db] = mfma(kt[db], sb, dq[db]);
-    }
-  }
-  if (!live) return;
-  bf16_t* dQ = (bf16_t*)a.dq + b * a.q_bstride + h * a.q_hstride + r * a.ldq;
-#pragma unroll
-  for (int db = 0; db < D::NDB; ++db) {
-    const int d = db * 16 + 4 * g;
-    if (d < HD) *reinterpret_cast<u32x2*>(dQ + d) = u32x2{pack2bf(dq[db][0], dq[db][1]), pack2bf(dq[db][2], dq[db][3])};
-  }
+  for (int kb = 0; kb < nkb; ++kb) q.step(mk, kv.ks(kb), kv.vs(kb), kb, lane);
+  q.store(a, u, lane, q.dq, 1.f);
 }
 
 // dK, dV with every query row (Q, dO, lse, delta) of the unit resident: grid (ceil(nk / 64), Z * H);
@@ -1148,9 +1168,9 @@ __global__ void __launch_bounds__(FR_NW * 64) flash_bwd_kv_res_kernel(pz_flash_a
       del_all[tr] = dv_;
     }
   }
-  f32x4 dk[D::NDB], dv[D::NDB];
+  f32x4 dk[D::NDB][1], dv[D::NDB][1];
 #pragma unroll
-  for (int db = 0; db < D::NDB; ++db) dk[db] = dv[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int db = 0; db < D::NDB; ++db) dk[db][0] = dv[db][0] = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
   bf16x8 kfr[D::NKS], vfr[D::NKS];
 #pragma unroll
@@ -1197,8 +1217,8 @@ __global__ void __launch_bounds__(FR_NW * 64) flash_bwd_kv_res_kernel(pz_flash_a
     const bf16x8 sb = pack8(ds[0], ds[1]);
 #pragma unroll
     for (int db = 0; db < D::NDB; ++db) {
-      dv[db] = mfma(frag_tr<D::ROW>(Ds, 0, db * 16, lane), pb, dv[db]);
-      dk[db] = mfma(frag_tr<D::ROW>(Qs, 0, db * 16, lane), sb, dk[db]);
+      dv[db][0] = mfma(frag_tr<D::ROW>(Ds, 0, db * 16, lane), pb, dv[db][0]);
+      dk[db][0] = mfma(frag_tr<D::ROW>(Qs, 0, db * 16, lane), sb, dk[db][0]);
     }
   }
   // query halves: waves 4..7 hand their partial sums to waves 0..3 through LDS (Q image reused)
@@ -1207,27 +1227,21 @@ __global__ void __launch_bounds__(FR_NW * 64) flash_bwd_kv_res_kernel(pz_flash_a
   if (qh == 1) {
 #pragma unroll
     for (int db = 0; db < D::NDB; ++db) {
-      red[((kw * D::NDB + db) * 2 + 0) * 64 + lane] = dk[db];
-      red[((kw * D::NDB + db) * 2 + 1) * 64 + lane] = dv[db];
+      red[((kw * D::NDB + db) * 2 + 0) * 64 + lane] = dk[db][0];
+      red[((kw * D::NDB + db) * 2 + 1) * 64 + lane] = dv[db][0];
     }
   }
   __syncthreads();
   if (qh == 1 || key >= a.nk) return;
 #pragma unroll
   for (int db = 0; db < D::NDB; ++db) {
-    dk[db] += red[((kw * D::NDB + db) * 2 + 0) * 64 + lane];
-    dv[db] += red[((kw * D::NDB + db) * 2 + 1) * 64 + lane];
+    dk[db][0] += red[((kw * D::NDB + db) * 2 + 0) * 64 + lane];
+    dv[db][0] += red[((kw * D::NDB + db) * 2 + 1) * 64 + lane];
   }
   bf16_t* dK = (bf16_t*)a.dk + b * a.k_bstride + h * a.k_hstride + (int64_t)key * a.ldk;
   bf16_t* dV = (bf16_t*)a.dv + b * a.v_bstride + h * a.v_hstride + (int64_t)key * a.ldv;
-#pragma unroll
-  for (int db = 0; db < D::NDB; ++db) {
-    const int d = db * 16 + 4 * g;
-    if (d < HD) {
-      *reinterpret_cast<u32x2*>(dK + d) = u32x2{pack2bf(dk[db][0], dk[db][1]), pack2bf(dk[db][2], dk[db][3])};
-      *reinterpret_cast<u32x2*>(dV + d) = u32x2{pack2bf(dv[db][0], dv[db][1]), pack2bf(dv[db][2], dv[db][3])};
-    }
-  }
+  fa_store_row<HD>(dK, dk, 0, g, 1.f);
+  fa_store_row<HD>(dV, dv, 0, g, 1.f);
 }
 
 constexpr int FR_SMEM_KQ = 2 * FR_MAX * FaDims<72>::ROW * 2;  // forward / dQ: K + V images
@@ -1252,34 +1266,20 @@ __device__ __forceinline__ int64_t fa_unit_of(const pz_flash_args& a) {
 }
 
 constexpr int FU_NW = 8;
+static_assert(FU_NW == FR_NW, "the resident images are staged by FR_NW waves");
 
 // PLAIN (no mask, no soft-cap: SigLIP): the element-wise softmax in the log2 domain with the scale
 // folded into one multiply and no mask / -inf guards -- the per-score VALU work, not the MFMAs,
 // bounds these head-72 kernels (5 instead of ~17 vector instructions per score)
-constexpr float FA_LOG2E = 1.4426950408889634f, FA_LN2 = 0.6931471805599453f;
-
 template <int HD, bool PLAIN>
 __global__ void __launch_bounds__(FU_NW * 64) flash_fwd_unit_kernel(pz_flash_args a) {
   using D = FaDims<HD>;
-  constexpr int NT = FU_NW * 64;
   extern __shared__ __attribute__((aligned(16))) char fa_smem[];
-  bf16_t* Kall = reinterpret_cast<bf16_t*>(fa_smem);
-  bf16_t* Vall = Kall + FR_MAX * D::ROW;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
   const int64_t zh = fa_unit_of(a), b = zh / a.H, h = zh % a.H;
-  const bf16_t* Q = (const bf16_t*)a.q + b * a.q_bstride + h * a.q_hstride;
-  const bf16_t* K = (const bf16_t*)a.k + b * a.k_bstride + h * a.k_hstride;
-  const bf16_t* V = (const bf16_t*)a.v + b * a.v_bstride + h * a.v_hstride;
   const FaMask mk(a, b);
-  {
-    TileStager<HD, D::ROW, FR_MAX, NT> stk, stv;
-    stk.load(K, a.ldk, 0, a.nk);
-    stv.load(V, a.ldv, 0, a.nk);
-    zero_pad_cols<HD, D::HDK, D::ROW, FR_MAX, NT>(Kall);
-    zero_pad_cols<HD, D::HDK, D::ROW, FR_MAX, NT>(Vall);
-    stk.store(Kall);
-    stv.store(Vall);
-  }
+  const FaResKV<HD> kv(a, FaUnit(a, zh), fa_smem);
+  const bf16_t* Q = kv.Q;
   bf16x8 qf[2][D::NKS];
   int t[2];
 #pragma unroll
@@ -1300,8 +1300,8 @@ __global__ void __launch_bounds__(FU_NW * 64) flash_fwd_unit_kernel(pz_flash_arg
   const int nkb = (int)((a.nk + FA_KB - 1) / FA_KB);
   __syncthreads();
   for (int kb = 0; kb < nkb; ++kb) {
-    const bf16_t* Ks = Kall + kb * FA_KB * D::ROW;
-    const bf16_t* Vs = Vall + kb * FA_KB * D::ROW;
+    const bf16_t* Ks = kv.ks(kb);
+    const bf16_t* Vs = kv.vs(kb);
     f32x4 sc[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) sc[i][0] = sc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1383,14 +1383,7 @@ __global__ void __launch_bounds__(FU_NW * 64) flash_fwd_unit_kernel(pz_flash_arg
     if (rq >= a.nq) continue;
     const float inv = l[qb] > 0.f ? 1.f / l[qb] : 0.f;
     const int gi = fr.grp(rq);
-    bf16_t* O = (bf16_t*)a.g_o[gi] + fr.off(b, h, rq, gi);
-#pragma unroll
-    for (int db = 0; db < D::NDB; ++db) {
-      const int d = db * 16 + 4 * g;
-      if (d < HD)
-        *reinterpret_cast<u32x2*>(O + d) =
-            u32x2{pack2bf(o[db][qb][0] * inv, o[db][qb][1] * inv), pack2bf(o[db][qb][2] * inv, o[db][qb][3] * inv)};
-    }
+    fa_store_row<HD>((bf16_t*)a.g_o[gi] + fr.off(b, h, rq, gi), o, qb, g, inv);
     if (g == 0 && a.lse) a.lse[zh * a.nq + rq] = PLAIN ? m[qb] * FA_LN2 + __logf(l[qb]) : m[qb] + __logf(l[qb]);
   }
 }
@@ -1398,131 +1391,17 @@ __global__ void __launch_bounds__(FU_NW * 64) flash_fwd_unit_kernel(pz_flash_arg
 // dQ (+ delta): one workgroup per unit, K / V resident, wave w owns query rows 32w .. 32w + 31
 template <int HD, bool PLAIN>
 __global__ void __launch_bounds__(FU_NW * 64) flash_bwd_q_unit_kernel(pz_flash_args a) {
-  using D = FaDims<HD>;
-  constexpr int NT = FU_NW * 64;
   extern __shared__ __attribute__((aligned(16))) char fa_smem[];
-  bf16_t* Kall = reinterpret_cast<bf16_t*>(fa_smem);
-  bf16_t* Vall = Kall + FR_MAX * D::ROW;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
-  const int64_t zh = fa_unit_of(a), b = zh / a.H, h = zh % a.H;
-  const bf16_t* Q = (const bf16_t*)a.q + b * a.q_bstride + h * a.q_hstride;
-  const bf16_t* K = (const bf16_t*)a.k + b * a.k_bstride + h * a.k_hstride;
-  const bf16_t* V = (const bf16_t*)a.v + b * a.v_bstride + h * a.v_hstride;
-  const FaMask mk(a, b);
-  const FaRow fr{&a};
-  {
-    TileStager<HD, D::ROW, FR_MAX, NT> stk, stv;
-    stk.load(K, a.ldk, 0, a.nk);
-    stv.load(V, a.ldv, 0, a.nk);
-    zero_pad_cols<HD, D::HDK, D::ROW, FR_MAX, NT>(Kall);
-    zero_pad_cols<HD, D::HDK, D::ROW, FR_MAX, NT>(Vall);
-    stk.store(Kall);
-    stv.store(Vall);
-  }
-  bf16x8 qf[2][D::NKS], df[2][D::NKS];
-  float del[2], lse[2];
-  int tq[2];
-  bool live[2];
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int64_t r = wave * 32 + qb * 16 + (lane & 15);
-    live[qb] = r < a.nq;
-    tq[qb] = mk.token((int)r);
-    const bf16_t* dOr = nullptr;
-    const bf16_t* Or = nullptr;
-    if (live[qb]) {
-      const int gi = fr.grp(r);
-      dOr = (const bf16_t*)a.g_do[gi] + fr.off(b, h, r, gi);
-      Or = (const bf16_t*)a.g_o[gi] + fr.off(b, h, r, gi);
-    }
-    float dl = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < D::NKS; ++ks) {
-      const int c = ks * 32 + 8 * g;
-      const bool ok = live[qb] && c < HD;
-      qf[qb][ks] = ok ? *reinterpret_cast<const bf16x8*>(Q + r * a.ldq + c) : bf16x8{};
-      df[qb][ks] = ok ? *reinterpret_cast<const bf16x8*>(dOr + c) : bf16x8{};
-      if (ok) {
-        const bf16x8 ov = *reinterpret_cast<const bf16x8*>(Or + c);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dl += (float)df[qb][ks][e] * (float)ov[e];
-      }
-    }
-    dl += __shfl_xor(dl, 16, 64);
-    dl += __shfl_xor(dl, 32, 64);
-    del[qb] = dl;
-    if (live[qb] && g == 0) a.delta[zh * a.nq + r] = dl;
-    lse[qb] = live[qb] ? a.lse[zh * a.nq + r] : 0.f;
-    if constexpr (PLAIN) lse[qb] *= FA_LOG2E;
-  }
-  const float sl2 = a.scale * FA_LOG2E;
-  f32x4 dq[D::NDB][2];
-#pragma unroll
-  for (int db = 0; db < D::NDB; ++db) dq[db][0] = dq[db][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const FaUnit u(a, fa_unit_of(a));
+  const FaMask mk(a, u.b);
+  const FaResKV<HD> kv(a, u, fa_smem);
+  FaDq<HD, 2, PLAIN> q;
+  q.init(a, mk, kv.Q, u, wave * 32, lane);
   const int nkb = (int)((a.nk + FA_KB - 1) / FA_KB);
   __syncthreads();
-  for (int kb = 0; kb < nkb; ++kb) {
-    const bf16_t* Ks = Kall + kb * FA_KB * D::ROW;
-    const bf16_t* Vs = Vall + kb * FA_KB * D::ROW;
-    f32x4 ds[4][2];  // dS^T[key 16i + 4g + e][query of block qb]
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      bf16x8 kfr[D::NKS], vfr[D::NKS];
-#pragma unroll
-      for (int ks = 0; ks < D::NKS; ++ks) {
-        kfr[ks] = frag_row<D::ROW>(Ks, i * 16, ks * 32, lane);
-        vfr[ks] = frag_row<D::ROW>(Vs, i * 16, ks * 32, lane);
-      }
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb) {
-        f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < D::NKS; ++ks) {
-          sv = mfma(kfr[ks], qf[qb][ks], sv);
-          dp = mfma(vfr[ks], df[qb][ks], dp);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int j = kb * FA_KB + i * 16 + 4 * g + e;
-          float dse = 0.f;
-          if constexpr (PLAIN) {  // keys past nk are zero rows of the K / V images: no contribution;
-            // dS without the scale (applied to dQ once, in the epilogue)
-            dse = __builtin_amdgcn_exp2f(sv[e] * sl2 - lse[qb]) * (dp[e] - del[qb]);
-          } else if (live[qb]) {
-            const FaLogit lg = fa_logit_d(mk, sv[e], tq[qb], j);
-            const float pe = lg.x == -INFINITY ? 0.f : __expf(lg.x - lse[qb]);
-            dse = pe * (dp[e] - del[qb]) * lg.dxds;
-          }
-          ds[i][qb][e] = dse;
-        }
-      }
-    }
-#pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {
-      const bf16x8 sb0 = pack8(ds[2 * k2][0], ds[2 * k2 + 1][0]);
-      const bf16x8 sb1 = pack8(ds[2 * k2][1], ds[2 * k2 + 1][1]);
-#pragma unroll
-      for (int db = 0; db < D::NDB; ++db) {
-        const bf16x8 kt = frag_tr<D::ROW>(Ks, k2 * 32, db * 16, lane);
-        dq[db][0] = mfma(kt, sb0, dq[db][0]);
-        dq[db][1] = mfma(kt, sb1, dq[db][1]);
-      }
-    }
-  }
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    if (!live[qb]) continue;
-    const int64_t r = wave * 32 + qb * 16 + (lane & 15);
-    bf16_t* dQ = (bf16_t*)a.dq + b * a.q_bstride + h * a.q_hstride + r * a.ldq;
-    const float f = PLAIN ? a.scale : 1.f;
-#pragma unroll
-    for (int db = 0; db < D::NDB; ++db) {
-      const int d = db * 16 + 4 * g;
-      if (d < HD)
-        *reinterpret_cast<u32x2*>(dQ + d) =
-            u32x2{pack2bf(dq[db][qb][0] * f, dq[db][qb][1] * f), pack2bf(dq[db][qb][2] * f, dq[db][qb][3] * f)};
-    }
-  }
+  for (int kb = 0; kb < nkb; ++kb) q.step(mk, kv.ks(kb), kv.vs(kb), kb, lane);
+  q.store(a, u, lane, q.dq, PLAIN ? a.scale : 1.f);
 }
 
 // dK, dV: one workgroup per unit, Q / dO / lse / delta resident; wave w owns keys 32w .. 32w + 31,
@@ -1640,17 +1519,8 @@ __global__ void __launch_bounds__(FU_NW * 64) flash_bwd_kv_unit_kernel(pz_flash_
     if (key[kb2] >= a.nk) continue;
     bf16_t* dK = (bf16_t*)a.dk + b * a.k_bstride + h * a.k_hstride + (int64_t)key[kb2] * a.ldk;
     bf16_t* dV = (bf16_t*)a.dv + b * a.v_bstride + h * a.v_hstride + (int64_t)key[kb2] * a.ldv;
-    const float f = PLAIN ? a.scale : 1.f;
-#pragma unroll
-    for (int db = 0; db < D::NDB; ++db) {
-      const int d = db * 16 + 4 * g;
-      if (d < HD) {
-        *reinterpret_cast<u32x2*>(dK + d) = u32x2{pack2bf(dk[db][kb2][0] * f, dk[db][kb2][1] * f),
-                                                  pack2bf(dk[db][kb2][2] * f, dk[db][kb2][3] * f)};
-        *reinterpret_cast<u32x2*>(dV + d) =
-            u32x2{pack2bf(dv[db][kb2][0], dv[db][kb2][1]), pack2bf(dv[db][kb2][2], dv[db][kb2][3])};
-      }
-    }
+    fa_store_row<HD>(dK, dk, kb2, g, PLAIN ? a.scale : 1.f);
+    fa_store_row<HD>(dV, dv, kb2, g, 1.f);
   }
 }
 
@@ -3020,21 +2890,8 @@ static bool fa_unit(const pz_flash_args* a) {
 // no mask, no soft-cap (SigLIP): the unit kernels' log2-domain element-wise fast path
 static bool fa_plain(const pz_flash_args* a) { return a->mask_mode == 0 && a->cap == 0.f; }
 
-// compute units of the current device (the persistent SigLIP grid: one workgroup per CU)
-static int fa_device_cus() {
-  static int cache[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (!cache[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cache[dev] = n;
-  }
-  return cache[dev];
-}
-
 // workgroups of the persistent SigLIP kernels: one per CU (units are taken from per-XCD ticket counters, FsTickets)
-static int fa_sig_grid(const pz_flash_args* a) { return (int)std::min<int64_t>(a->Z * a->H, fa_device_cus()); }
+static int fa_sig_grid(const pz_flash_args* a) { return (int)std::min<int64_t>(a->Z * a->H, pz_device_cus()); }
 
 // the SigLIP training shape (256 x 256 keys, head 72, plain, one output group): the persistent pipelined
 // kernels; PZ_FLASH_SIG "0" keeps the one-workgroup-per-unit kernels (tests, A/B runs)
@@ -3047,130 +2904,140 @@ static bool fa_sig(const pz_flash_args* a) {
          a->g_ld[0] * FS_N < (1 << 30);
 }
 
-// Raise the kernel's dynamic-LDS limit once; a refusal is cleared here (the launch is checked on
-// its own) so it cannot surface as a later launch's error
-template <class Kern>
-static void fa_smem_attr(Kern k, int bytes, bool& done) {
+// which kernel form a call takes: the step-staged general kernels, the resident 2- / 4-workgroup kernels, one
+// workgroup per unit (plain / masked or soft-capped), or the persistent SigLIP kernels (the knobs are read per call)
+enum FaRoute { FA_GENERAL, FA_RESIDENT, FA_UNIT_PLAIN, FA_UNIT_MASKED, FA_PERSISTENT };
+static FaRoute fa_route(const pz_flash_args* a) {
+  if (!fa_resident(a)) return FA_GENERAL;
+  if (!fa_unit(a)) return FA_RESIDENT;
+  if (fa_sig(a)) return FA_PERSISTENT;
+  return fa_plain(a) ? FA_UNIT_PLAIN : FA_UNIT_MASKED;
+}
+
+// Launch with dynamic LDS.  The kernel's dynamic-LDS limit is raised once (one flag per kernel); a refusal is
+// cleared here (the launch is checked on its own) so it cannot surface as a later launch's error
+template <auto Kern, class... Args>
+static void fa_launch_smem(dim3 grid, dim3 block, int bytes, hipStream_t st, Args... args) {
+  static bool done = false;
   if (!done) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
       (void)hipGetLastError();
     done = true;
   }
+  hipLaunchKernelGGL(Kern, grid, block, bytes, st, args...);
 }
 
-extern "C" int pz_flash_fwd(const pz_flash_args* a, void* stream) {
-  PZ_CHECK_ARG(a && a->q && a->k && a->v && a->Z > 0 && a->H > 0 && a->nq > 0 && a->nk > 0,
-               "flash_fwd: bad args");
-  PZ_CHECK_ARG(fa_hd_ok(a->head_dim), "flash_fwd: head_dim %lld unsupported (16, 32, 72, 256)",
-               (long long)a->head_dim);
-  PZ_CHECK_ARG(a->n_groups >= 1 && a->n_groups <= 3 && a->g_row0[0] == 0, "flash_fwd: output groups");
-  for (int i = 0; i < a->n_groups; ++i) PZ_CHECK_ARG(a->g_o[i] && a->g_ld[i] % 4 == 0, "flash_fwd: group %d", i);
-  PZ_CHECK_ARG(PZ_ALIGNED(a->q, 16) && PZ_ALIGNED(a->k, 16) && PZ_ALIGNED(a->v, 16) && a->ldq % 8 == 0 &&
-                   a->ldk % 8 == 0 && a->ldv % 8 == 0 && a->q_hstride % 8 == 0 && a->k_hstride % 8 == 0 &&
-                   a->v_hstride % 8 == 0 && a->q_bstride % 8 == 0 && a->k_bstride % 8 == 0 &&
-                   a->v_bstride % 8 == 0 && a->o_hstride % 4 == 0,
-               "flash_fwd: operands need 16-byte aligned rows");
-  if (a->mask_mode == 1) PZ_CHECK_ARG(a->cnt && a->rows_per_token > 0, "flash_fwd: block mask needs cnt");
-  PZ_CHECK_ARG(a->nq + a->mask_row0 < (1 << 22) && a->nk < (1 << 22) && a->mask_row0 >= 0, "flash_fwd: nq/nk too large");
-  PZ_CHECK_ARG(a->Z * a->H < 65536, "flash_fwd: too many units");
-  const int64_t qblk = (a->nq + 127) / 128, units = qblk * a->Z * a->H;  // 128 query rows per workgroup
-  // few workgroups (inference: one action chunk, one prefix): split the keys over up to 16
-  // workgroups per unit when the caller gave a workspace for the partials
-  const int64_t nkb = (a->nk + FA_KB - 1) / FA_KB;
+// ---- operand checks shared by the entry points (fn: the entry point's name in the message) ----
+static bool fa_sizes_ok(const pz_flash_args* a) { return a->Z > 0 && a->H > 0 && a->nq > 0 && a->nk > 0; }
+static bool fa_qkv_rows16(const pz_flash_args* a) {  // 16-byte aligned q / k / v rows and batch strides
+  return PZ_ALIGNED(a->q, 16) && PZ_ALIGNED(a->k, 16) && PZ_ALIGNED(a->v, 16) && a->ldq % 8 == 0 && a->ldk % 8 == 0 &&
+         a->ldv % 8 == 0 && a->q_bstride % 8 == 0 && a->k_bstride % 8 == 0 && a->v_bstride % 8 == 0;
+}
+static bool fa_mask_ok(const pz_flash_args* a) {
+  return a->mask_mode == 0 || (a->mask_mode == 1 && a->cnt && a->rows_per_token > 0);
+}
+static int fa_check_groups(const pz_flash_args* a, const char* fn) {
+  PZ_CHECK_ARG(a->n_groups >= 1 && a->n_groups <= 3 && a->g_row0[0] == 0, "%s: output groups", fn);
+  return PZ_OK;
+}
+static int fa_check_group_o(const pz_flash_args* a, const char* fn) {
+  for (int i = 0; i < a->n_groups; ++i) PZ_CHECK_ARG(a->g_o[i] && a->g_ld[i] % 4 == 0, "%s: group %d", fn, i);
+  return PZ_OK;
+}
+#define FA_CHECK(call)                 \
+  do {                                 \
+    if (int rc_ = (call)) return rc_;  \
+  } while (0)
+
+// forward key split: few workgroups (inference: one action chunk, one prefix) split the keys over up to 16
+// workgroups per unit when the caller gave a workspace for the (O, m, l) partials; wgs = workgroups unsplit
+static int64_t fa_key_split(const pz_flash_args* a, int64_t wgs, int64_t nkb) {
   int64_t sp = 1;
-  if (a->ws && units < 128 && nkb > 1 && a->head_dim % 4 == 0) {
-    sp = (256 + units - 1) / units;
+  if (a->ws && wgs < 128 && nkb > 1 && a->head_dim % 4 == 0) {
+    sp = (256 + wgs - 1) / wgs;
     sp = sp < nkb ? sp : nkb;
     sp = sp < 16 ? sp : 16;
     while (sp > 1 && sp * a->Z * a->H * a->nq * (a->head_dim + 2) * 4 > a->ws_bytes) --sp;
     const int64_t per = (nkb + sp - 1) / sp;
     sp = (nkb + per - 1) / per;  // no empty split
   }
-  dim3 grid((unsigned)qblk, (unsigned)(a->Z * a->H), (unsigned)sp);
+  return sp;
+}
+
+extern "C" int pz_flash_fwd(const pz_flash_args* a, void* stream) {
+  PZ_CHECK_ARG(a && a->q && a->k && a->v && fa_sizes_ok(a), "flash_fwd: bad args");
+  PZ_CHECK_ARG(fa_hd_ok(a->head_dim), "flash_fwd: head_dim %lld unsupported (16, 32, 72, 256)",
+               (long long)a->head_dim);
+  FA_CHECK(fa_check_groups(a, "flash_fwd"));
+  FA_CHECK(fa_check_group_o(a, "flash_fwd"));
+  PZ_CHECK_ARG(fa_qkv_rows16(a) && a->q_hstride % 8 == 0 && a->k_hstride % 8 == 0 && a->v_hstride % 8 == 0 &&
+                   a->o_hstride % 4 == 0,
+               "flash_fwd: operands need 16-byte aligned rows");
+  if (a->mask_mode == 1) PZ_CHECK_ARG(a->cnt && a->rows_per_token > 0, "flash_fwd: block mask needs cnt");
+  PZ_CHECK_ARG(a->nq + a->mask_row0 < (1 << 22) && a->nk < (1 << 22) && a->mask_row0 >= 0, "flash_fwd: nq/nk too large");
+  PZ_CHECK_ARG(a->Z * a->H < 65536, "flash_fwd: too many units");
+  const int64_t units = a->Z * a->H, qblk = (a->nq + 127) / 128;  // 128 query rows per workgroup
+  const int64_t sp = fa_key_split(a, qblk * units, (a->nk + FA_KB - 1) / FA_KB);
   hipStream_t st = (hipStream_t)stream;
-  if (sp == 1 && fa_resident(a) && fa_unit(a)) {
-    static bool attr = false;
-    static bool attr2 = false;
-    static bool attr3 = false;
-    const dim3 gu((unsigned)(a->Z * a->H));
-    if (fa_sig(a)) {
+  const dim3 gu((unsigned)units), bu(FU_NW * 64);
+  switch (sp == 1 ? fa_route(a) : FA_GENERAL) {  // only the general kernel splits keys
+    case FA_PERSISTENT: {
       const int G = fa_sig_grid(a);
-      (void)attr3;
-      {
-        static bool attr4 = false;
-        fa_smem_attr(flash_fwd_sig_kernel<1>, FS_SMEM, attr4);
-        hipLaunchKernelGGL(flash_fwd_sig_kernel<1>, dim3((unsigned)G), dim3(16 * 64), FS_SMEM, st, *a, G);
-      }
-    } else if (fa_plain(a)) {
-      fa_smem_attr(flash_fwd_unit_kernel<72, true>, FR_SMEM_KQ, attr);
-      hipLaunchKernelGGL((flash_fwd_unit_kernel<72, true>), gu, dim3(FU_NW * 64), FR_SMEM_KQ, st, *a);
-    } else {
-      fa_smem_attr(flash_fwd_unit_kernel<72, false>, FR_SMEM_KQ, attr2);
-      hipLaunchKernelGGL((flash_fwd_unit_kernel<72, false>), gu, dim3(FU_NW * 64), FR_SMEM_KQ, st, *a);
+      fa_launch_smem<flash_fwd_sig_kernel<1>>(dim3((unsigned)G), dim3(16 * 64), FS_SMEM, st, *a, G);
+      break;
     }
-    PZ_CHECK_LAUNCH();
-    return PZ_OK;
+    case FA_UNIT_PLAIN: fa_launch_smem<flash_fwd_unit_kernel<72, true>>(gu, bu, FR_SMEM_KQ, st, *a); break;
+    case FA_UNIT_MASKED: fa_launch_smem<flash_fwd_unit_kernel<72, false>>(gu, bu, FR_SMEM_KQ, st, *a); break;
+    case FA_RESIDENT:
+      fa_launch_smem<flash_fwd_res_kernel<72>>(dim3((unsigned)((a->nq + FR_NW * 16 - 1) / (FR_NW * 16) * units)),
+                                               dim3(FR_NW * 64), FR_SMEM_KQ, st, *a);
+      break;
+    case FA_GENERAL:
+      FA_DISPATCH(a->head_dim, flash_fwd_kernel, dim3((unsigned)qblk, (unsigned)units, (unsigned)sp),
+                  dim3((a->head_dim == 256 ? 8 : 4) * 64), 0, st, *a);
+      if (sp > 1) {
+        PZ_CHECK_LAUNCH();
+        const int64_t n = units * a->nq * (a->head_dim / 4);
+        FA_DISPATCH(a->head_dim, flash_fwd_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *a,
+                    (int)sp);
+      }
+      break;
   }
-  if (sp == 1 && fa_resident(a)) {
-    static bool attr = false;
-    fa_smem_attr(flash_fwd_res_kernel<72>, FR_SMEM_KQ, attr);
-    hipLaunchKernelGGL(flash_fwd_res_kernel<72>, dim3((unsigned)((a->nq + FR_NW * 16 - 1) / (FR_NW * 16) * a->Z * a->H)),
-                       dim3(FR_NW * 64), FR_SMEM_KQ, st, *a);
-    PZ_CHECK_LAUNCH();
-    return PZ_OK;
-  }
-  FA_DISPATCH(a->head_dim, flash_fwd_kernel, grid, dim3((a->head_dim == 256 ? 8 : 4) * 64), 0, st, *a);
   PZ_CHECK_LAUNCH();
-  if (sp > 1) {
-    const int64_t n = a->Z * a->H * a->nq * (a->head_dim / 4);
-    FA_DISPATCH(a->head_dim, flash_fwd_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *a,
-                (int)sp);
-    PZ_CHECK_LAUNCH();
-  }
   return PZ_OK;
 }
 
-
 extern "C" int pz_flash_fwd_probs(const pz_flash_args* a, void* P, void* tcap, int64_t ldp, void* stream) {
-  PZ_CHECK_ARG(a && a->q && a->k && a->v && P && a->Z > 0 && a->H > 0 && a->nq > 0 && a->nk > 0,
-               "flash_fwd_probs: bad args");
+  PZ_CHECK_ARG(a && a->q && a->k && a->v && P && fa_sizes_ok(a), "flash_fwd_probs: bad args");
   PZ_CHECK_ARG(a->head_dim == 256, "flash_fwd_probs: head_dim %lld (256 only)", (long long)a->head_dim);
   PZ_CHECK_ARG(a->nk <= JP_MAXKB * FA_KB && ldp >= a->nk && ldp % 4 == 0, "flash_fwd_probs: nk %lld / ldp %lld",
                (long long)a->nk, (long long)ldp);
-  PZ_CHECK_ARG(a->mask_mode == 0 || (a->mask_mode == 1 && a->cnt && a->rows_per_token > 0),
-               "flash_fwd_probs: mask mode %d", a->mask_mode);
-  PZ_CHECK_ARG(a->n_groups >= 1 && a->n_groups <= 3 && a->g_row0[0] == 0, "flash_fwd_probs: output groups");
-  for (int i = 0; i < a->n_groups; ++i) PZ_CHECK_ARG(a->g_o[i] && a->g_ld[i] % 4 == 0, "flash_fwd_probs: group %d", i);
-  PZ_CHECK_ARG(PZ_ALIGNED(a->q, 16) && PZ_ALIGNED(a->k, 16) && PZ_ALIGNED(a->v, 16) && PZ_ALIGNED(P, 8) &&
-                   (!tcap || PZ_ALIGNED(tcap, 8)) && a->ldq % 8 == 0 && a->ldk % 8 == 0 && a->ldv % 8 == 0 &&
-                   a->q_bstride % 8 == 0 && a->k_bstride % 8 == 0 && a->v_bstride % 8 == 0,
+  PZ_CHECK_ARG(fa_mask_ok(a), "flash_fwd_probs: mask mode %d", a->mask_mode);
+  FA_CHECK(fa_check_groups(a, "flash_fwd_probs"));
+  FA_CHECK(fa_check_group_o(a, "flash_fwd_probs"));
+  PZ_CHECK_ARG(fa_qkv_rows16(a) && PZ_ALIGNED(P, 8) && (!tcap || PZ_ALIGNED(tcap, 8)),
                "flash_fwd_probs: operands need 16-byte aligned rows");
   PZ_CHECK_ARG(a->nq + a->mask_row0 < (1 << 22) && a->Z * a->H < 65536, "flash_fwd_probs: nq / units too large");
   const int64_t units = a->Z * a->H, nqb = (a->nq + JP_NW * 16 - 1) / (JP_NW * 16);
-  {
-    static bool attr0 = false, attr1 = false;
-    if (a->cap > 0.f) {
-      fa_smem_attr(flash_fwd_probs_dma_kernel<true>, JD_SMEM, attr1);
-      hipLaunchKernelGGL(flash_fwd_probs_dma_kernel<true>, dim3((unsigned)(nqb * units)), dim3(JP_NW * 64), JD_SMEM,
-                         (hipStream_t)stream, *a, (bf16_t*)P, (bf16_t*)tcap, ldp);
-    } else {
-      fa_smem_attr(flash_fwd_probs_dma_kernel<false>, JD_SMEM, attr0);
-      hipLaunchKernelGGL(flash_fwd_probs_dma_kernel<false>, dim3((unsigned)(nqb * units)), dim3(JP_NW * 64), JD_SMEM,
-                         (hipStream_t)stream, *a, (bf16_t*)P, (bf16_t*)tcap, ldp);
-    }
-    PZ_CHECK_LAUNCH();
-    return PZ_OK;
-  }
+  const dim3 grid((unsigned)(nqb * units)), block(JP_NW * 64);
+  if (a->cap > 0.f)
+    fa_launch_smem<flash_fwd_probs_dma_kernel<true>>(grid, block, JD_SMEM, (hipStream_t)stream, *a, (bf16_t*)P,
+                                                     (bf16_t*)tcap, ldp);
+  else
+    fa_launch_smem<flash_fwd_probs_dma_kernel<false>>(grid, block, JD_SMEM, (hipStream_t)stream, *a, (bf16_t*)P,
+                                                      (bf16_t*)tcap, ldp);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
 }
 
 extern "C" int pz_flash_bwd_ds(const pz_flash_args* a, const void* P, const void* tcap, void* dS, int64_t ldp,
                                void* stream) {
-  PZ_CHECK_ARG(a && a->v && P && dS && a->Z > 0 && a->H > 0 && a->nq > 0 && a->nk > 0, "flash_bwd_ds: bad args");
+  PZ_CHECK_ARG(a && a->v && P && dS && fa_sizes_ok(a), "flash_bwd_ds: bad args");
   PZ_CHECK_ARG(a->head_dim == 256, "flash_bwd_ds: head_dim %lld (256 only)", (long long)a->head_dim);
   PZ_CHECK_ARG(a->nk <= JP_MAXKB * FA_KB && ldp >= a->nk && ldp % 4 == 0, "flash_bwd_ds: nk %lld / ldp %lld",
                (long long)a->nk, (long long)ldp);
   PZ_CHECK_ARG(a->cap <= 0.f || tcap, "flash_bwd_ds: soft-cap needs tcap");
-  PZ_CHECK_ARG(a->n_groups >= 1 && a->n_groups <= 3 && a->g_row0[0] == 0, "flash_bwd_ds: output groups");
+  FA_CHECK(fa_check_groups(a, "flash_bwd_ds"));
   for (int i = 0; i < a->n_groups; ++i) PZ_CHECK_ARG(!a->g_do[i] || a->g_ld[i] % 8 == 0, "flash_bwd_ds: dO group %d", i);
   PZ_CHECK_ARG(PZ_ALIGNED(a->v, 16) && a->ldv % 8 == 0 && a->v_bstride % 8 == 0 && PZ_ALIGNED(P, 8) &&
                    PZ_ALIGNED(dS, 8) && (!tcap || PZ_ALIGNED(tcap, 8)),
@@ -3181,10 +3048,8 @@ extern "C" int pz_flash_bwd_ds(const pz_flash_args* a, const void* P, const void
                  "flash_bwd_ds: dQ needs K (16-byte rows) and an 8-byte aligned dQ");
   PZ_CHECK_ARG(a->Z * a->H < 65536, "flash_bwd_ds: too many units");
   const int64_t units = a->Z * a->H, nqb = (a->nq + JP_NW * 16 - 1) / (JP_NW * 16);
-  static bool attr = false;
-  fa_smem_attr(flash_bwd_ds_dma_kernel, JD_SMEM, attr);
-  hipLaunchKernelGGL(flash_bwd_ds_dma_kernel, dim3((unsigned)(nqb * units)), dim3(JP_NW * 64), JD_SMEM,
-                     (hipStream_t)stream, *a, (const bf16_t*)P, (const bf16_t*)tcap, (bf16_t*)dS, ldp);
+  fa_launch_smem<flash_bwd_ds_dma_kernel>(dim3((unsigned)(nqb * units)), dim3(JP_NW * 64), JD_SMEM, (hipStream_t)stream,
+                                          *a, (const bf16_t*)P, (const bf16_t*)tcap, (bf16_t*)dS, ldp);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
 }
@@ -3216,57 +3081,44 @@ extern "C" int pz_flash_bwd(const pz_flash_args* a, void* stream) {
     while (splits > 1 && splits * 2 * a->Z * a->H * a->nk * a->head_dim * 4 > a->ws_bytes) --splits;
   }
   // dQ pass first: it also writes delta, which the dK/dV pass reads
-  if (fa_resident(a) && fa_unit(a)) {
-    static bool aq = false, akv = false, aq2 = false, akv2 = false, aq3 = false, akv3 = false;
-    const dim3 gu((unsigned)(a->Z * a->H));
-    if (fa_sig(a)) {  // delta pass, then the persistent dQ and dK / dV kernels
-      const int G = fa_sig_grid(a);
-      fa_smem_attr(flash_bwd_kv_sig_kernel, FS_SMEM, akv3);
-      (void)aq3;
-      {
-        static bool aq4 = false;
-        fa_smem_attr(flash_bwd_q_sig_kernel<true>, FS_SMEM, aq4);
-        hipLaunchKernelGGL(flash_bwd_q_sig_kernel<true>, dim3((unsigned)G), dim3(FS_NW * 64), FS_SMEM, st, *a, G);
-      }
+  const int64_t units = a->Z * a->H;
+  const dim3 gu((unsigned)units), bu(FU_NW * 64);
+  switch (fa_route(a)) {
+    case FA_GENERAL: break;  // the step-staged kernels, below
+    case FA_PERSISTENT: {
+      const dim3 G((unsigned)fa_sig_grid(a)), bs(FS_NW * 64);
+      fa_launch_smem<flash_bwd_q_sig_kernel<true>>(G, bs, FS_SMEM, st, *a, (int)G.x);
       PZ_CHECK_LAUNCH();
-      hipLaunchKernelGGL(flash_bwd_kv_sig_kernel, dim3((unsigned)G), dim3(FS_NW * 64), FS_SMEM, st, *a, G);
-    } else if (fa_plain(a)) {
-      fa_smem_attr(flash_bwd_q_unit_kernel<72, true>, FR_SMEM_KQ, aq);
-      fa_smem_attr(flash_bwd_kv_unit_kernel<72, true>, FU_SMEM_KV, akv);
-      hipLaunchKernelGGL((flash_bwd_q_unit_kernel<72, true>), gu, dim3(FU_NW * 64), FR_SMEM_KQ, st, *a);
+      fa_launch_smem<flash_bwd_kv_sig_kernel>(G, bs, FS_SMEM, st, *a, (int)G.x);
       PZ_CHECK_LAUNCH();
-      hipLaunchKernelGGL((flash_bwd_kv_unit_kernel<72, true>), gu, dim3(FU_NW * 64), FU_SMEM_KV, st, *a);
-    } else {
-      fa_smem_attr(flash_bwd_q_unit_kernel<72, false>, FR_SMEM_KQ, aq2);
-      fa_smem_attr(flash_bwd_kv_unit_kernel<72, false>, FU_SMEM_KV, akv2);
-      hipLaunchKernelGGL((flash_bwd_q_unit_kernel<72, false>), gu, dim3(FU_NW * 64), FR_SMEM_KQ, st, *a);
-      PZ_CHECK_LAUNCH();
-      hipLaunchKernelGGL((flash_bwd_kv_unit_kernel<72, false>), gu, dim3(FU_NW * 64), FU_SMEM_KV, st, *a);
+      return PZ_OK;
     }
-    PZ_CHECK_LAUNCH();
-    return PZ_OK;
-  }
-  if (fa_resident(a)) {
-    static bool aq = false, akv = false;
-    fa_smem_attr(flash_bwd_q_res_kernel<72>, FR_SMEM_KQ, aq);
-    fa_smem_attr(flash_bwd_kv_res_kernel<72>, FR_SMEM_KV, akv);
-    hipLaunchKernelGGL(flash_bwd_q_res_kernel<72>, dim3((unsigned)((a->nq + FR_NW * 16 - 1) / (FR_NW * 16) * a->Z * a->H)),
-                       dim3(FR_NW * 64), FR_SMEM_KQ, st, *a);
-    PZ_CHECK_LAUNCH();
-    hipLaunchKernelGGL(flash_bwd_kv_res_kernel<72>, dim3((unsigned)(nkb * a->Z * a->H)), dim3(FR_NW * 64),
-                       FR_SMEM_KV, st, *a);
-    PZ_CHECK_LAUNCH();
-    return PZ_OK;
+    case FA_UNIT_PLAIN:
+      fa_launch_smem<flash_bwd_q_unit_kernel<72, true>>(gu, bu, FR_SMEM_KQ, st, *a);
+      PZ_CHECK_LAUNCH();
+      fa_launch_smem<flash_bwd_kv_unit_kernel<72, true>>(gu, bu, FU_SMEM_KV, st, *a);
+      PZ_CHECK_LAUNCH();
+      return PZ_OK;
+    case FA_UNIT_MASKED:
+      fa_launch_smem<flash_bwd_q_unit_kernel<72, false>>(gu, bu, FR_SMEM_KQ, st, *a);
+      PZ_CHECK_LAUNCH();
+      fa_launch_smem<flash_bwd_kv_unit_kernel<72, false>>(gu, bu, FU_SMEM_KV, st, *a);
+      PZ_CHECK_LAUNCH();
+      return PZ_OK;
+    case FA_RESIDENT:
+      fa_launch_smem<flash_bwd_q_res_kernel<72>>(dim3((unsigned)((a->nq + FR_NW * 16 - 1) / (FR_NW * 16) * units)),
+                                                 dim3(FR_NW * 64), FR_SMEM_KQ, st, *a);
+      PZ_CHECK_LAUNCH();
+      fa_launch_smem<flash_bwd_kv_res_kernel<72>>(dim3((unsigned)(nkb * units)), dim3(FR_NW * 64), FR_SMEM_KV, st, *a);
+      PZ_CHECK_LAUNCH();
+      return PZ_OK;
   }
   const int fm = fa_fast_bwd(a);
-  {
-    const int64_t units = a->Z * a->H, nqb = (a->nq + JQ_NW * 32 - 1) / (JQ_NW * 32);
-    const dim3 gq2((unsigned)(nqb * units));
-    if (fm == 2) {
-      FA_DISPATCH(a->head_dim, FA_T2(flash_bwd_q2_kernel, true), gq2, dim3(JQ_NW * 64), 0, st, *a);
-    } else {
-      FA_DISPATCH(a->head_dim, FA_T2(flash_bwd_q2_kernel, false), gq2, dim3(JQ_NW * 64), 0, st, *a);
-    }
+  const dim3 gq2((unsigned)((a->nq + JQ_NW * 32 - 1) / (JQ_NW * 32) * units));
+  if (fm == 2) {
+    FA_DISPATCH(a->head_dim, FA_T2(flash_bwd_q2_kernel, true), gq2, dim3(JQ_NW * 64), 0, st, *a);
+  } else {
+    FA_DISPATCH(a->head_dim, FA_T2(flash_bwd_q2_kernel, false), gq2, dim3(JQ_NW * 64), 0, st, *a);
   }
   PZ_CHECK_LAUNCH();
   const dim3 gkv1((unsigned)(nkb * a->Z * a->H * splits));
@@ -3287,7 +3139,7 @@ extern "C" int pz_flash_bwd(const pz_flash_args* a, void* stream) {
 
 extern "C" int pz_flash_fwd_f8(const pz_flash_args* a, const void* qc, const float* qs, const void* kc, const float* ks,
                                int64_t krows, const void* vtc, const float* vs, int64_t ldvt, void* stream) {
-  PZ_CHECK_ARG(a && qc && qs && kc && ks && vtc && vs && a->Z > 0 && a->nq > 0 && a->nk > 0 && a->H == 1,
+  PZ_CHECK_ARG(a && qc && qs && kc && ks && vtc && vs && fa_sizes_ok(a) && a->H == 1,
                "flash_fwd_f8: bad args (one K / V head: H == 1)");
   PZ_CHECK_ARG(a->head_dim == 256, "flash_fwd_f8: head_dim %lld (256 only)", (long long)a->head_dim);
   PZ_CHECK_ARG(krows >= a->nk && ldvt >= (a->nk + F8_KB - 1) / F8_KB * F8_KB && ldvt % 16 == 0,
@@ -3296,25 +3148,15 @@ extern "C" int pz_flash_fwd_f8(const pz_flash_args* a, const void* qc, const flo
   PZ_CHECK_ARG(PZ_ALIGNED(qc, 16) && PZ_ALIGNED(kc, 16) && PZ_ALIGNED(vtc, 16) && PZ_ALIGNED(vs, 16),
                "flash_fwd_f8: 16-byte aligned codes / scales");
   PZ_CHECK_ARG(a->n_groups >= 1 && a->n_groups <= 3 && a->g_row0[0] == 0 && a->o_hstride == 0, "flash_fwd_f8: groups");
-  for (int i = 0; i < a->n_groups; ++i) PZ_CHECK_ARG(a->g_o[i] && a->g_ld[i] % 4 == 0, "flash_fwd_f8: group %d", i);
-  PZ_CHECK_ARG(a->mask_mode == 0 || (a->mask_mode == 1 && a->cnt && a->rows_per_token > 0), "flash_fwd_f8: mask");
+  FA_CHECK(fa_check_group_o(a, "flash_fwd_f8"));
+  PZ_CHECK_ARG(fa_mask_ok(a), "flash_fwd_f8: mask");
   PZ_CHECK_ARG(a->nq + a->mask_row0 < (1 << 22) && a->Z < 65536, "flash_fwd_f8: nq / Z too large");
   const int64_t qblk = (a->nq + 127) / 128, nkb = (a->nk + F8_KB - 1) / F8_KB;
   // key split (few query blocks: the B = 1 prefill) into the caller's workspace, whenever fewer than 128 workgroups
-  int64_t sp = 1;
-  if (a->ws && qblk * a->Z < 128 && nkb > 1) {
-    sp = (256 + qblk * a->Z - 1) / (qblk * a->Z);
-    sp = sp < nkb ? sp : nkb;
-    sp = sp < 16 ? sp : 16;
-    while (sp > 1 && sp * a->Z * a->nq * (256 + 2) * 4 > a->ws_bytes) --sp;
-    const int64_t per = (nkb + sp - 1) / sp;
-    sp = (nkb + per - 1) / per;
-  }
-  static bool attr = false;
-  fa_smem_attr(flash_fwd_f8_kernel, F8_SMEM, attr);
+  const int64_t sp = fa_key_split(a, qblk * a->Z, nkb);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(flash_fwd_f8_kernel, dim3((unsigned)qblk, (unsigned)a->Z, (unsigned)sp), dim3(512), F8_SMEM, st, *a,
-                     (const uint8_t*)qc, qs, (const uint8_t*)kc, ks, krows, (const uint8_t*)vtc, vs, ldvt);
+  fa_launch_smem<flash_fwd_f8_kernel>(dim3((unsigned)qblk, (unsigned)a->Z, (unsigned)sp), dim3(512), F8_SMEM, st, *a,
+                                      (const uint8_t*)qc, qs, (const uint8_t*)kc, ks, krows, (const uint8_t*)vtc, vs, ldvt);
   PZ_CHECK_LAUNCH();
   if (sp > 1) {
     const int64_t n = a->Z * a->nq * 64;

@@ -1646,19 +1646,6 @@ struct Plan {
   int tall_mi;                     // tall-tile kernel: 64 * tall_mi rows per tile (4 | 5)
 };
 
-// compute units of the current device (the "wave" of resident 8-phase workgroups: 1 per CU)
-int device_cus() {
-  static int cache[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (!cache[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cache[dev] = n;
-  }
-  return cache[dev];
-}
-
 // Wave quantisation of the 8-phase kernel (one 256x256 tile per CU at a time): T = q*G + r tiles
 // leave the last round r/G full.  Split each of the r leftover tiles into s K-pieces (s*r <= G)
 // so the last round takes ~1/s of a tile time; partial sums go through the fp32 workspace.
@@ -1667,7 +1654,7 @@ void plan_tail(Plan& pl, const pz_gemm_args* a) {
   if (a->batch != 1 || !a->workspace || !PZ_ALIGNED(a->workspace, 16)) return;
   const char* e = getenv("PZ_GEMM_TAIL");  // "0": whole tiles only (A/B runs; read per call)
   if (e && e[0] == '0') return;
-  const int64_t G = device_cus();
+  const int64_t G = pz_device_cus();
   const int64_t T = pl.tiles_m * pl.tiles_n;
   const int64_t q = T / G, r = T % G;
   const int64_t nk = (a->K + 63) / 64;
@@ -1904,7 +1891,7 @@ Plan make_plan(const pz_gemm_args* a) {
     const int min_nc = e ? atoi(e) : 16;
     pl.skinny_nc = 16;
     while (pl.skinny_nc > 4 && pl.skinny_nc / 2 >= min_nc &&
-           a->batch * ((ncols + pl.skinny_nc - 1) / pl.skinny_nc) < device_cus())
+           a->batch * ((ncols + pl.skinny_nc - 1) / pl.skinny_nc) < pz_device_cus())
       pl.skinny_nc /= 2;
     pl.tiles_n = (ncols + pl.skinny_nc - 1) / pl.skinny_nc;
     return pl;
