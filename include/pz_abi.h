@@ -378,6 +378,41 @@ int pz_euler_step(float* action, const void* v, int64_t ldv, int64_t v_bstride, 
                   int64_t A, float dt, void* stream);
 int pz_clamp(float* x, int64_t n, float lo, float hi, void* stream);
 
+/* Action-prefix conditioning ("real-time chunking").  prefix_len: int32 [B] on the device, never NULL here;
+ * row h of sample b is a prefix row iff h < prefix_len[b].  Sibling entry points added under ABI 22: no existing
+ * signature, kernel or result changes, and with every prefix_len[b] == 0 each gives its sibling's bits.
+ *   pz_flow_psi_prefix         psi of a prefix row = bf16(x1) (no noise term)
+ *   pz_concat_time_prefix      a prefix row's time columns = the pz_time_embed bits of 1.0f (either mode)
+ *   pz_flow_loss_prefix        sum over the non-prefix rows / (A * sum_b (H - d_b)), the count taken from prefix_len on
+ *                              the device; dv = 0 on prefix rows
+ *   pz_time_embed_rows_prefix, pz_action_in_prefix   a prefix row's flow time is 1.0f
+ *   pz_action_out_prefix, pz_euler_step_prefix       a prefix row is not updated; t += dt for every sample
+ *   pz_action_prefix_init      action[b, h, :] = prefix[b, h, :] for h < d_b (fp32 [B, H, A]; other rows untouched)
+ *   pz_clamp_prefix            pz_clamp on the non-prefix rows of fp32 [B, H, A]
+ * prefix_len lives on the device and is not range-checked by the kernels: values outside [0, H] behave as 0 / H.  The
+ * callers keep d_b <= H - 1; with every d_b >= H no row carries loss and pz_flow_loss_prefix divides by zero (NaN). */
+int pz_flow_psi_prefix(const float* x0, const float* x1, const float* t, const int32_t* prefix_len, void* psi,
+                       int64_t B, int64_t H, int64_t A, float sig_min, void* stream);
+int pz_concat_time_prefix(const void* temb, const void* e1, void* out, const int32_t* prefix_len, int64_t B, int64_t H,
+                          int64_t D, float max_period, int32_t mode, void* stream);
+int pz_flow_loss_prefix(const void* v, int64_t ldv, int64_t v_bstride, const float* x0, const float* x1,
+                        const int32_t* prefix_len, float* loss, void* dv, const float* grad_scale, int64_t B,
+                        int64_t H, int64_t A, float sig_min, void* stream);
+int pz_time_embed_rows_prefix(const float* t, void* out, int64_t ldo, const int32_t* prefix_len, int64_t B, int64_t H,
+                              int64_t D, float max_period, int32_t mode, void* stream);
+int pz_action_in_prefix(const float* action, int64_t A, const void* w1, const void* b1, const float* t, void* cat,
+                        int64_t ldc, const int32_t* prefix_len, int64_t B, int64_t H, int64_t D, float max_period,
+                        int32_t mode, void* stream);
+int pz_action_out_prefix(const void* x, int64_t ldx, const void* norm_w, float eps, const void* wd, const void* bd,
+                         int64_t D, int64_t A, float* action, float* t, const int32_t* prefix_len, int64_t B,
+                         int64_t H, float dt, void* stream);
+int pz_euler_step_prefix(float* action, const void* v, int64_t ldv, int64_t v_bstride, float* t,
+                         const int32_t* prefix_len, int64_t B, int64_t H, int64_t A, float dt, void* stream);
+int pz_action_prefix_init(float* action, const float* prefix, const int32_t* prefix_len, int64_t B, int64_t H,
+                          int64_t A, void* stream);
+int pz_clamp_prefix(float* x, const int32_t* prefix_len, int64_t B, int64_t H, int64_t A, float lo, float hi,
+                    void* stream);
+
 /* elementwise backward of fused MLP epilogues (recompute activations, no extra saves) */
 int pz_geglu_bwd(const void* dh, int64_t lddh, const void* gu, int64_t ldgu, void* dgu, void* h_out,
                  int64_t ldh, int64_t M, int64_t I, void* stream);
@@ -534,6 +569,15 @@ int pz_proprio_normalize(const void* x, void* y, int64_t rows, int64_t D, const 
                          void* stream);
 int pz_action_denormalize(const void* x, void* y, int64_t rows, int64_t D, int64_t n_pass, const void* a,
                           const void* b, int32_t mode, void* stream);
+/*  pz_action_normalize: the inverse of pz_action_denormalize -- pz_proprio_normalize's formula (the bound
+ * form with its clip to [-1, 1]) on the first D - n_pass dimensions of every row, the trailing n_pass copied.
+ * pz_action_denormalize_prefix: pz_action_denormalize of x fp32 [B, H, D], except that rows h < prefix_len[b] of y are
+ * copied bit for bit from prev fp32 [B, H, D] (the robot-unit actions the caller committed to). */
+int pz_action_normalize(const void* x, void* y, int64_t rows, int64_t D, int64_t n_pass, const void* a, const void* b,
+                        int32_t mode, void* stream);
+int pz_action_denormalize_prefix(const void* x, void* y, const void* prev, const int32_t* prefix_len, int64_t B,
+                                 int64_t H, int64_t D, int64_t n_pass, const void* a, const void* b, int32_t mode,
+                                 void* stream);
 
 /* Training-image augmentation (csrc/pz_augment.hip, pz_image_resize_u8 in csrc/pz_obs.hip): the random
  * crop and colour jitter of the reference's data pipeline (src/agent/dataset.py:38-70, dlimp/augmentations.py) as

@@ -116,27 +116,44 @@ __device__ __forceinline__ bf16_t time_embed_col(float tb, int j, int D, float m
   return f2bf(j < half ? sinf(a) : cosf(a));
 }
 
+// Action-prefix conditioning: row h of sample b is a prefix row iff h < prefix_len[b].  A prefix row is
+// fed clean: its flow time is 1 and no Euler step updates it.  The kernels below that take a sample's t are templates
+// on PFX; the <false> forms are the kernels as they were (prefix_len is not read), the <true> forms are launched by
+// the pz_*_prefix entry points only.
+template <bool PFX>
+__device__ __forceinline__ float row_time(const float* __restrict__ t, const int32_t* __restrict__ pl, int64_t r,
+                                          int64_t H) {
+  if (PFX) {
+    if ((int64_t)pl[r / H] > r % H) return 1.f;
+  }
+  return t[r / H];
+}
+
+template <bool PFX>
 __global__ void time_embed_rows_kernel(const float* __restrict__ t, bf16_t* out, int64_t ldo, int64_t rows,
-                                       int64_t H, int D, float max_period, int mode) {
+                                       int64_t H, int D, float max_period, int mode,
+                                       const int32_t* __restrict__ pl) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= rows * D) return;
   const int64_t r = idx / D;
   const int j = (int)(idx % D);
-  out[r * ldo + j] = time_embed_col(t[r / H], j, D, max_period, mode);
+  out[r * ldo + j] = time_embed_col(row_time<PFX>(t, pl, r, H), j, D, max_period, mode);
 }
 
 // Denoise-step input in one launch (inference): cat[r] = [time embedding of sample r / H | linear_1(bf16(action[r]))]
 // -- the bf16 cast, the 7 -> D action Linear (gemm_small_kernel's arithmetic: fp32 sum over k in order, bias, one
 // bf16 rounding) and time_embed_rows_kernel, bit for bit, in one launch instead of three
+template <bool PFX>
 __global__ void action_in_kernel(const float* __restrict__ action, int64_t A, const bf16_t* __restrict__ W1,
                                  const bf16_t* __restrict__ b1, const float* __restrict__ t, bf16_t* cat, int64_t ldc,
-                                 int64_t rows, int64_t H, int D, float max_period, int mode) {
+                                 int64_t rows, int64_t H, int D, float max_period, int mode,
+                                 const int32_t* __restrict__ pl) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= rows * 2 * D) return;
   const int64_t r = idx / (2 * D);
   const int j = (int)(idx % (2 * D));
   if (j < D) {
-    cat[r * ldc + j] = time_embed_col(t[r / H], j, D, max_period, mode);
+    cat[r * ldc + j] = time_embed_col(row_time<PFX>(t, pl, r, H), j, D, max_period, mode);
     return;
   }
   const int n = j - D;
@@ -166,12 +183,14 @@ __global__ void action_in_kernel(const float* __restrict__ action, int64_t A, co
 // (rmsnorm_fwd_kernel's arithmetic: 8-element chunks lane + 64 c, fp32 sum of squares, y = x r (1 + w) rounded to
 // bf16), the D -> A action decoder (gemm_small_rowwave_kernel's arithmetic on the same chunks, butterfly sum, bias,
 // bf16 v) and the Euler update action += dt v (euler_kernel), bit for bit -- one launch instead of three.  D <= 1024,
-// D % 8 == 0, A <= 8.
+// D % 8 == 0, A <= 8.  PFX: a prefix row's action is left as it is; its sample's t advances all the same (the lane
+// that owns row h == 0 does that, and row 0 is a prefix row whenever prefix_len >= 1).
+template <bool PFX>
 __global__ void __launch_bounds__(256) action_out_kernel(const bf16_t* __restrict__ x, int64_t ldx,
                                                          const bf16_t* __restrict__ nw, float eps,
                                                          const bf16_t* __restrict__ Wd, const bf16_t* __restrict__ bd,
                                                          int D, int A, float* action, float* t, int64_t rows,
-                                                         int64_t H, float dt) {
+                                                         int64_t H, float dt, const int32_t* __restrict__ pl) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -253,7 +272,9 @@ __global__ void __launch_bounds__(256) action_out_kernel(const bf16_t* __restric
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s[n] += __shfl_xor(s[n], off);
   }
-  if (lane < A) {
+  bool upd = lane < A;
+  if (PFX) upd = upd && !((int64_t)pl[row / H] > row % H);
+  if (upd) {
     float o = 0.f;
 #pragma unroll
     for (int n = 0; n < NMAX; ++n)
@@ -271,6 +292,22 @@ __global__ void concat_time_kernel(const bf16_t* __restrict__ temb, const bf16_t
   if (idx >= rows * 2 * D) return;
   const int64_t r = idx / (2 * D), c = idx % (2 * D);
   out[idx] = c < D ? temb[(r / H) * D + c] : e1[r * D + c - D];
+}
+
+// training concat with a prefix: a prefix row's time columns are the embedding of 1.0f (time_embed_kernel's
+// arithmetic through time_embed_col), every other row's come from temb as above
+__global__ void concat_time_prefix_kernel(const bf16_t* __restrict__ temb, const bf16_t* __restrict__ e1, bf16_t* out,
+                                          const int32_t* __restrict__ pl, int64_t rows, int64_t H, int D,
+                                          float max_period, int mode) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * 2 * D) return;
+  const int64_t r = idx / (2 * D);
+  const int c = (int)(idx % (2 * D));
+  if (c >= D) {
+    out[idx] = e1[r * D + c - D];
+    return;
+  }
+  out[idx] = (int64_t)pl[r / H] > r % H ? time_embed_col(1.f, c, D, max_period, mode) : temb[(r / H) * D + c];
 }
 
 __global__ void split_time_grad_kernel(const bf16_t* __restrict__ dcat, bf16_t* de1, int64_t rows, int64_t D) {
@@ -318,6 +355,77 @@ __global__ void euler_kernel(float* action, const bf16_t* __restrict__ v, int64_
   if (t && idx < B) t[idx] += dt;
 }
 
+// ---- the prefix forms of the flow-matching kernels ----
+// psi of a prefix row is bf16(x1): the clean action, no noise term
+__global__ void flow_psi_prefix_kernel(const float* x0, const float* x1, const float* t,
+                                       const int32_t* __restrict__ pl, bf16_t* psi, int64_t B, int64_t H, int64_t A,
+                                       float sig) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t HA = H * A;
+  if (idx >= B * HA) return;
+  const int64_t b = idx / HA, h = (idx % HA) / A;
+  if ((int64_t)pl[b] > h) {
+    psi[idx] = f2bf(x1[idx]);
+    return;
+  }
+  const float tt = t[b];
+  psi[idx] = f2bf((1.f - (1.f - sig) * tt) * x0[idx] + tt * x1[idx]);
+}
+
+// flow_loss_kernel over the non-prefix rows: the element count A * sum_b (H - d_b) comes from prefix_len on the
+// device (every thread sums the B integers: no host sync, no second launch); dv is 0 on prefix rows.  With every
+// d_b = 0 the terms, their order and the divisor are flow_loss_kernel's.
+__global__ void flow_loss_prefix_kernel(const bf16_t* __restrict__ v, int64_t ldv, int64_t vbs,
+                                        const float* __restrict__ x0, const float* __restrict__ x1,
+                                        const int32_t* __restrict__ pl, float* loss, bf16_t* dv,
+                                        const float* __restrict__ gscale, int64_t H, int64_t rows, int64_t A,
+                                        float sig) {
+  __shared__ float red[4];
+  const int64_t n = rows * A;
+  int64_t live = 0;
+  for (int64_t b = 0; b < rows / H; ++b) {
+    const int64_t d = pl[b];
+    live += H - (d < 0 ? 0 : d > H ? H : d);
+  }
+  const int64_t cnt = live * A;
+  float s = 0.f;
+  const float g = gscale ? gscale[0] : 1.f;
+  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+    const int64_t r = i / A, c = i % A;
+    const int64_t vo = (r / H) * vbs + (r % H) * ldv + c;
+    if ((int64_t)pl[r / H] > r % H) {
+      if (dv) dv[vo] = 0;
+      continue;
+    }
+    const float d = x1[i] - (1.f - sig) * x0[i];
+    const float e = bf2f(v[vo]) - d;
+    s += e * e;
+    if (dv) dv[vo] = f2bf(g * 2.f * e / (float)cnt);
+  }
+  s = block_sum<4>(s, red);
+  if (threadIdx.x == 0) loss[0] = s / (float)cnt;
+}
+
+__global__ void euler_prefix_kernel(float* action, const bf16_t* __restrict__ v, int64_t ldv, int64_t vbs, float* t,
+                                    const int32_t* __restrict__ pl, int64_t B, int64_t H, int64_t A, float dt) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx < B * H * A) {
+    const int64_t r = idx / A, c = idx % A;
+    if (!((int64_t)pl[r / H] > r % H)) action[idx] += dt * bf2f(v[(r / H) * vbs + (r % H) * ldv + c]);
+  }
+  if (t && idx < B) t[idx] += dt;
+}
+
+// the action buffer's prefix rows before the first step: action[b, h, :] = prefix[b, h, :] for h < d_b (the other rows
+// keep the noise they hold)
+__global__ void prefix_init_kernel(float* action, const float* __restrict__ prefix, const int32_t* __restrict__ pl,
+                                   int64_t n, int64_t H, int64_t A) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const int64_t r = idx / A;
+  if ((int64_t)pl[r / H] > r % H) action[idx] = prefix[idx];
+}
+
 
 __global__ void copy_rows_kernel(const bf16_t* __restrict__ src, int64_t sld, int64_t sbs, bf16_t* dst, int64_t dld,
                                  int64_t dbs, int64_t rows, int64_t D, float scale, int beta) {
@@ -334,6 +442,15 @@ __global__ void copy_rows_kernel(const bf16_t* __restrict__ src, int64_t sld, in
 __global__ void clamp_kernel(float* x, int64_t n, float lo, float hi) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < n) x[idx] = fminf(fmaxf(x[idx], lo), hi);
+}
+
+// the final action clamp with prefix rows exempt: they are returned as given
+__global__ void clamp_prefix_kernel(float* x, const int32_t* __restrict__ pl, int64_t n, int64_t H, int64_t A,
+                                    float lo, float hi) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const int64_t r = idx / A;
+  if (!((int64_t)pl[r / H] > r % H)) x[idx] = fminf(fmaxf(x[idx], lo), hi);
 }
 
 __global__ void geglu_bwd_kernel(const bf16_t* __restrict__ dh, int64_t lddh, const bf16_t* gu, int64_t ldgu,
@@ -539,8 +656,19 @@ extern "C" int pz_time_embed_rows(const float* t, void* out, int64_t ldo, int64_
                                   float max_period, int32_t mode, void* stream) {
   PZ_CHECK_ARG(t && out && B > 0 && H > 0 && D >= 4 && D % 2 == 0 && ldo >= D && (mode == 0 || mode == 1),
                "time_embed_rows: bad args");
-  hipLaunchKernelGGL(time_embed_rows_kernel, dim3(nblk(B * H * D)), dim3(256), 0, ST, t, (bf16_t*)out, ldo, B * H, H,
-                     (int)D, max_period, (int)mode);
+  hipLaunchKernelGGL(time_embed_rows_kernel<false>, dim3(nblk(B * H * D)), dim3(256), 0, ST, t, (bf16_t*)out, ldo,
+                     B * H, H, (int)D, max_period, (int)mode, (const int32_t*)nullptr);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_time_embed_rows_prefix(const float* t, void* out, int64_t ldo, const int32_t* prefix_len, int64_t B,
+                                         int64_t H, int64_t D, float max_period, int32_t mode, void* stream) {
+  PZ_CHECK_ARG(t && out && prefix_len && B > 0 && H > 0 && D >= 4 && D % 2 == 0 && ldo >= D &&
+                   (mode == 0 || mode == 1),
+               "time_embed_rows_prefix: bad args");
+  hipLaunchKernelGGL(time_embed_rows_kernel<true>, dim3(nblk(B * H * D)), dim3(256), 0, ST, t, (bf16_t*)out, ldo,
+                     B * H, H, (int)D, max_period, (int)mode, prefix_len);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
 }
@@ -550,8 +678,22 @@ extern "C" int pz_action_in(const float* action, int64_t A, const void* w1, cons
   PZ_CHECK_ARG(action && w1 && t && cat && A > 0 && B > 0 && H > 0 && D >= 4 && D % 2 == 0 && ldc >= 2 * D &&
                    (mode == 0 || mode == 1),
                "action_in: bad args");
-  hipLaunchKernelGGL(action_in_kernel, dim3(nblk(B * H * 2 * D)), dim3(256), 0, ST, action, A, (const bf16_t*)w1,
-                     (const bf16_t*)b1, t, (bf16_t*)cat, ldc, B * H, H, (int)D, max_period, (int)mode);
+  hipLaunchKernelGGL(action_in_kernel<false>, dim3(nblk(B * H * 2 * D)), dim3(256), 0, ST, action, A,
+                     (const bf16_t*)w1, (const bf16_t*)b1, t, (bf16_t*)cat, ldc, B * H, H, (int)D, max_period,
+                     (int)mode, (const int32_t*)nullptr);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_action_in_prefix(const float* action, int64_t A, const void* w1, const void* b1, const float* t,
+                                   void* cat, int64_t ldc, const int32_t* prefix_len, int64_t B, int64_t H, int64_t D,
+                                   float max_period, int32_t mode, void* stream) {
+  PZ_CHECK_ARG(action && w1 && t && cat && prefix_len && A > 0 && B > 0 && H > 0 && D >= 4 && D % 2 == 0 &&
+                   ldc >= 2 * D && (mode == 0 || mode == 1),
+               "action_in_prefix: bad args");
+  hipLaunchKernelGGL(action_in_kernel<true>, dim3(nblk(B * H * 2 * D)), dim3(256), 0, ST, action, A,
+                     (const bf16_t*)w1, (const bf16_t*)b1, t, (bf16_t*)cat, ldc, B * H, H, (int)D, max_period,
+                     (int)mode, prefix_len);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
 }
@@ -563,9 +705,24 @@ extern "C" int pz_action_out(const void* x, int64_t ldx, const void* norm_w, flo
                    D % 8 == 0 && ldx % 8 == 0 && PZ_ALIGNED(x, 16) && PZ_ALIGNED(norm_w, 16) && PZ_ALIGNED(wd, 16),
                "action_out: D <= 1024, D %% 8 == 0, A <= 8, 16-byte aligned rows");
   const int64_t rows = B * H;
-  hipLaunchKernelGGL(action_out_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ST, (const bf16_t*)x, ldx,
-                     (const bf16_t*)norm_w, eps, (const bf16_t*)wd, (const bf16_t*)bd, (int)D, (int)A, action, t, rows,
-                     H, dt);
+  hipLaunchKernelGGL(action_out_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ST, (const bf16_t*)x,
+                     ldx, (const bf16_t*)norm_w, eps, (const bf16_t*)wd, (const bf16_t*)bd, (int)D, (int)A, action, t,
+                     rows, H, dt, (const int32_t*)nullptr);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_action_out_prefix(const void* x, int64_t ldx, const void* norm_w, float eps, const void* wd,
+                                    const void* bd, int64_t D, int64_t A, float* action, float* t,
+                                    const int32_t* prefix_len, int64_t B, int64_t H, float dt, void* stream) {
+  PZ_CHECK_ARG(x && norm_w && wd && action && prefix_len && B > 0 && H > 0 && A >= 1 && A <= 8 && D >= 8 &&
+                   D <= 1024 && D % 8 == 0 && ldx % 8 == 0 && PZ_ALIGNED(x, 16) && PZ_ALIGNED(norm_w, 16) &&
+                   PZ_ALIGNED(wd, 16),
+               "action_out_prefix: D <= 1024, D %% 8 == 0, A <= 8, 16-byte aligned rows");
+  const int64_t rows = B * H;
+  hipLaunchKernelGGL(action_out_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ST, (const bf16_t*)x,
+                     ldx, (const bf16_t*)norm_w, eps, (const bf16_t*)wd, (const bf16_t*)bd, (int)D, (int)A, action, t,
+                     rows, H, dt, prefix_len);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
 }
@@ -575,6 +732,16 @@ extern "C" int pz_concat_time(const void* temb, const void* e1, void* out, int64
   PZ_CHECK_ARG(temb && e1 && out && B > 0 && H > 0 && D > 0, "concat_time: bad args");
   hipLaunchKernelGGL(concat_time_kernel, dim3(nblk(B * H * 2 * D)), dim3(256), 0, ST, (const bf16_t*)temb,
                      (const bf16_t*)e1, (bf16_t*)out, B * H, H, D);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_concat_time_prefix(const void* temb, const void* e1, void* out, const int32_t* prefix_len, int64_t B,
+                                     int64_t H, int64_t D, float max_period, int32_t mode, void* stream) {
+  PZ_CHECK_ARG(temb && e1 && out && prefix_len && B > 0 && H > 0 && D >= 4 && D % 2 == 0 && (mode == 0 || mode == 1),
+               "concat_time_prefix: bad args");
+  hipLaunchKernelGGL(concat_time_prefix_kernel, dim3(nblk(B * H * 2 * D)), dim3(256), 0, ST, (const bf16_t*)temb,
+                     (const bf16_t*)e1, (bf16_t*)out, prefix_len, B * H, H, (int)D, max_period, (int)mode);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
 }
@@ -612,6 +779,55 @@ extern "C" int pz_euler_step(float* action, const void* v, int64_t ldv, int64_t 
   const int64_t n = B * H * A > B ? B * H * A : B;
   hipLaunchKernelGGL(euler_kernel, dim3(nblk(n)), dim3(256), 0, ST, action, (const bf16_t*)v, ldv, v_bstride, t, B,
                      H, A, dt);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_flow_psi_prefix(const float* x0, const float* x1, const float* t, const int32_t* prefix_len, void* psi,
+                                  int64_t B, int64_t H, int64_t A, float sig_min, void* stream) {
+  PZ_CHECK_ARG(x0 && x1 && t && prefix_len && psi && B > 0 && H > 0 && A > 0, "flow_psi_prefix: bad args");
+  hipLaunchKernelGGL(flow_psi_prefix_kernel, dim3(nblk(B * H * A)), dim3(256), 0, ST, x0, x1, t, prefix_len,
+                     (bf16_t*)psi, B, H, A, sig_min);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_flow_loss_prefix(const void* v, int64_t ldv, int64_t v_bstride, const float* x0, const float* x1,
+                                   const int32_t* prefix_len, float* loss, void* dv, const float* grad_scale,
+                                   int64_t B, int64_t H, int64_t A, float sig_min, void* stream) {
+  PZ_CHECK_ARG(v && x0 && x1 && prefix_len && loss && B > 0 && H > 0 && A > 0, "flow_loss_prefix: bad args");
+  hipLaunchKernelGGL(flow_loss_prefix_kernel, dim3(1), dim3(256), 0, ST, (const bf16_t*)v, ldv, v_bstride, x0, x1,
+                     prefix_len, loss, (bf16_t*)dv, grad_scale, H, B * H, A, sig_min);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_euler_step_prefix(float* action, const void* v, int64_t ldv, int64_t v_bstride, float* t,
+                                    const int32_t* prefix_len, int64_t B, int64_t H, int64_t A, float dt,
+                                    void* stream) {
+  PZ_CHECK_ARG(action && v && prefix_len && B > 0 && H > 0 && A > 0, "euler_step_prefix: bad args");
+  const int64_t n = B * H * A > B ? B * H * A : B;
+  hipLaunchKernelGGL(euler_prefix_kernel, dim3(nblk(n)), dim3(256), 0, ST, action, (const bf16_t*)v, ldv, v_bstride,
+                     t, prefix_len, B, H, A, dt);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_action_prefix_init(float* action, const float* prefix, const int32_t* prefix_len, int64_t B,
+                                     int64_t H, int64_t A, void* stream) {
+  PZ_CHECK_ARG(action && prefix && prefix_len && action != prefix && B > 0 && H > 0 && A > 0,
+               "action_prefix_init: bad args");
+  hipLaunchKernelGGL(prefix_init_kernel, dim3(nblk(B * H * A)), dim3(256), 0, ST, action, prefix, prefix_len,
+                     B * H * A, H, A);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_clamp_prefix(float* x, const int32_t* prefix_len, int64_t B, int64_t H, int64_t A, float lo,
+                               float hi, void* stream) {
+  PZ_CHECK_ARG(x && prefix_len && B > 0 && H > 0 && A > 0, "clamp_prefix: bad args");
+  hipLaunchKernelGGL(clamp_prefix_kernel, dim3(nblk(B * H * A)), dim3(256), 0, ST, x, prefix_len, B * H * A, H, A,
+                     lo, hi);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
 }

@@ -126,6 +126,54 @@ __global__ void __launch_bounds__(OBS_THREADS) action_denorm_kernel(const float*
   y[i] = o;
 }
 
+// action_denorm_kernel's inverse (robot units -> the model's normalised actions: the committed prefix of DESIGN 7f):
+// proprio_norm_kernel's two formulas on the first D - n_pass dimensions, the trailing ones copied
+__global__ void __launch_bounds__(OBS_THREADS) action_norm_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                  int64_t total, int D, int n_pass,
+                                                                  const float* __restrict__ a,
+                                                                  const float* __restrict__ b, int mode) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x;
+  if (i >= total) return;
+  const int j = (int)(i % D);
+  const float v = x[i];
+  float o = v;
+  if (j < D - n_pass) {
+    const float p = a[j], q = b[j];
+    if (mode == MODE_BOUND) {
+      o = 2.f * (v - p) / (q - p + 1e-8f) - 1.f;
+      o = fminf(fmaxf(o, -1.f), 1.f);
+    } else {
+      o = (v - p) / (q + 1e-8f);
+    }
+  }
+  y[i] = o;
+}
+
+// action_denorm_kernel with the committed prefix passed through: rows h < prefix_len[b] of the [B, H, D] output are
+// the caller's robot-unit rows `prev`, bit for bit (what the robot executed is what is returned for those steps)
+__global__ void __launch_bounds__(OBS_THREADS) action_denorm_prefix_kernel(
+    const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ prev,
+    const int32_t* __restrict__ pl, int64_t total, int64_t H, int D, int n_pass, const float* __restrict__ a,
+    const float* __restrict__ b, int mode) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x;
+  if (i >= total) return;
+  const int j = (int)(i % D);
+  const int64_t r = i / D;
+  if ((int64_t)pl[r / H] > r % H) {
+    y[i] = prev[i];
+    return;
+  }
+  const float v = x[i];
+  float o = v;
+  if (j < D - n_pass) {
+    const float p = a[j], q = b[j];
+    o = mode == MODE_BOUND ? (v + 1.f) / 2.f * (q - p) + p : v * (q + 1e-8f) + p;
+  }
+  y[i] = o;
+}
+
 inline bool obs_grid(int64_t total, unsigned* blocks) {
   const int64_t nb = (total + OBS_THREADS - 1) / OBS_THREADS;
   if (nb < 1 || nb > 0x7fffffffll) return false;
@@ -243,6 +291,35 @@ extern "C" int pz_action_denormalize(const void* x, void* y, int64_t rows, int64
   PZ_CHECK_ARG(obs_grid(rows * D, &g), "action_denormalize: too many elements for one launch");
   hipLaunchKernelGGL(action_denorm_kernel, dim3(g), dim3(OBS_THREADS), 0, ST, (const float*)x, (float*)y, rows * D,
                      (int)D, (int)n_pass, (const float*)a, (const float*)b, (int)mode);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_action_normalize(const void* x, void* y, int64_t rows, int64_t D, int64_t n_pass, const void* a,
+                                   const void* b, int32_t mode, void* stream) {
+  if (int rc = obs_norm_check("action_normalize", x, y, rows, D, a, b, mode)) return rc;
+  PZ_CHECK_ARG(n_pass >= 0 && n_pass <= D, "action_normalize: n_pass must be in [0, D]");
+  unsigned g;
+  PZ_CHECK_ARG(obs_grid(rows * D, &g), "action_normalize: too many elements for one launch");
+  hipLaunchKernelGGL(action_norm_kernel, dim3(g), dim3(OBS_THREADS), 0, ST, (const float*)x, (float*)y, rows * D,
+                     (int)D, (int)n_pass, (const float*)a, (const float*)b, (int)mode);
+  PZ_CHECK_LAUNCH();
+  return PZ_OK;
+}
+
+extern "C" int pz_action_denormalize_prefix(const void* x, void* y, const void* prev, const int32_t* prefix_len,
+                                            int64_t B, int64_t H, int64_t D, int64_t n_pass, const void* a,
+                                            const void* b, int32_t mode, void* stream) {
+  PZ_CHECK_ARG(B > 0 && H > 0, "action_denormalize_prefix: B and H must be positive");
+  if (int rc = obs_norm_check("action_denormalize_prefix", x, y, B * H, D, a, b, mode)) return rc;
+  PZ_CHECK_ARG(prev && prefix_len && PZ_ALIGNED(prev, 4) && PZ_ALIGNED(prefix_len, 4),
+               "action_denormalize_prefix: null or misaligned prev / prefix_len");
+  PZ_CHECK_ARG(n_pass >= 0 && n_pass <= D, "action_denormalize_prefix: n_pass must be in [0, D]");
+  unsigned g;
+  PZ_CHECK_ARG(obs_grid(B * H * D, &g), "action_denormalize_prefix: too many elements for one launch");
+  hipLaunchKernelGGL(action_denorm_prefix_kernel, dim3(g), dim3(OBS_THREADS), 0, ST, (const float*)x, (float*)y,
+                     (const float*)prev, prefix_len, B * H * D, H, (int)D, (int)n_pass, (const float*)a,
+                     (const float*)b, (int)mode);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
 }

@@ -197,6 +197,18 @@ SIGNATURES = {
     "pz_image_resize_norm": [vp, i32, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, vp],
     "pz_proprio_normalize": [vp, vp, i64, i64, vp, vp, i32, vp],
     "pz_action_denormalize": [vp, vp, i64, i64, i64, vp, vp, i32, vp],
+    # action-prefix conditioning: sibling entry points, prefix_len = int32 [B]
+    "pz_flow_psi_prefix": [vp, vp, vp, vp, vp, i64, i64, i64, f32, vp],
+    "pz_concat_time_prefix": [vp, vp, vp, vp, i64, i64, i64, f32, i32, vp],
+    "pz_flow_loss_prefix": [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, f32, vp],
+    "pz_time_embed_rows_prefix": [vp, vp, i64, vp, i64, i64, i64, f32, i32, vp],
+    "pz_action_in_prefix": [vp, i64, vp, vp, vp, vp, i64, vp, i64, i64, i64, f32, i32, vp],
+    "pz_action_out_prefix": [vp, i64, vp, f32, vp, vp, i64, i64, vp, vp, vp, i64, i64, f32, vp],
+    "pz_euler_step_prefix": [vp, vp, i64, i64, vp, vp, i64, i64, i64, f32, vp],
+    "pz_action_prefix_init": [vp, vp, vp, i64, i64, i64, vp],
+    "pz_clamp_prefix": [vp, vp, i64, i64, i64, f32, f32, vp],
+    "pz_action_normalize": [vp, vp, i64, i64, i64, vp, vp, i32, vp],
+    "pz_action_denormalize_prefix": [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, i32, vp],
     "pz_image_augment_scratch_bytes": [i64, i64],
     "pz_image_augment": [vp, i32, i64, i64, vp, vp, i32, vp, vp, i64, vp, vp],
     "pz_image_resize_u8": [vp, i32, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp],

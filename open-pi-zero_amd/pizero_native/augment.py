@@ -121,14 +121,30 @@ def parse_kwargs(kwargs):
     return [parse_spec(k) for k in kwargs]
 
 
-def generator(seed, cnt_batch, rank):
+def generator(seed, cnt_batch, rank, stream=0):
     """Philox keyed on the seed, with (cnt_batch, rank) in the two high counter words: the draws of one micro-batch
-    advance the low word only, so no two (seed, cnt_batch, rank) share any part of a stream."""
+    advance the low word only, so no two (seed, cnt_batch, rank) share any part of a stream.  ``stream`` (a 64-bit
+    constant, 0 for the image augmentation) goes into the key's high word: another consumer of the same seed draws
+    from a stream of its own."""
     m = (1 << 64) - 1
     if cnt_batch < 0 or rank < 0:
         raise ValueError("draw_params: cnt_batch and rank must be non-negative")
-    return np.random.Generator(np.random.Philox(key=[int(seed) & m, (int(seed) >> 64) & m],
+    return np.random.Generator(np.random.Philox(key=[int(seed) & m, ((int(seed) >> 64) ^ int(stream)) & m],
                                                 counter=[0, 0, int(cnt_batch) & m, int(rank) & m]))
+
+
+PREFIX_STREAM = 0x7072656669785F64  # "prefix_d": the action-prefix delays' stream (DESIGN 7f)
+
+
+def draw_prefix_len(bsz, max_delay, seed, cnt_batch, rank=0):
+    """int64 [bsz] numpy: one delay d ~ U{0..max_delay} per sample of micro-batch ``cnt_batch``, from the
+    generator above under PREFIX_STREAM -- a function of (seed, cnt_batch, rank) alone, so ranks differ and neither
+    the augmentation's draws nor torch's generator are touched.  TrainAgent passes the number of micro-batches consumed
+    (``micro_batches_seen``, which a resume restores), so a resumed run continues the draws."""
+    bsz, max_delay = int(bsz), int(max_delay)
+    if bsz < 1 or max_delay < 0:
+        raise ValueError(f"draw_prefix_len: bsz must be positive and max_delay non-negative, got {bsz}, {max_delay}")
+    return generator(seed, cnt_batch, rank, stream=PREFIX_STREAM).integers(0, max_delay + 1, size=bsz)
 
 
 def draw_params(specs, n_frames, seed, cnt_batch, rank=0, crop_draws="shared"):

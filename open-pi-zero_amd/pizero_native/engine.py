@@ -187,6 +187,9 @@ def _mask_kw(d, cnt, which):
 
 FP8_ADAPTIVE_MSG = ("fp8 inference is not available with action_expert_adaptive_mode (adaLN / adaLN-Zero): the fp8 "
                     "norm-to-codes kernels are Gemma-RMSNorm specific and the reference has no fp8 path")
+PREFIX_ADAPTIVE_MSG = ("an action prefix (action_prefix_max_delay / prefix_len, DESIGN 7f) is not available with "
+                       "action_expert_adaptive_mode (adaLN / adaLN-Zero): the adaLN condition is one time per sample, "
+                       "and a prefix row needs its own (time 1)")
 
 
 class Ada:
@@ -958,11 +961,14 @@ class Engine:
         self._b3s_version = self.weights_version()
         return True
 
-    def action_embed(self, psi_bf, t, save):
+    def action_embed(self, psi_bf, t, save, prefix_len=None):
         """ActionEncoder (vla/modules.py:39-53) with time embedding (vla/modules.py:15-22).  Inference (save None):
         the first Linear and the time embedding write straight into the concat input (pz_time_embed_rows: no
-        separate embedding buffer or concat launch) and no pre-activation is kept."""
+        separate embedding buffer or concat launch) and no pre-activation is kept.  ``prefix_len`` (int32 [B], DESIGN
+        7f): the time columns of rows h < prefix_len[b] are the embedding of 1.0."""
         d = self.d
+        if d.ada and prefix_len is not None:
+            raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
         rows = psi_bf.shape[0]
         B = t.shape[0]
         dev = psi_bf.device
@@ -983,7 +989,7 @@ class Engine:
             cat = torch.empty(rows, 2 * d.aH, device=dev, dtype=BF16)
             ops.small_linear(psi_bf, self.w("action_encoder.linear_1.weight"), cat[:, d.aH:],
                              bias=self.w("action_encoder.linear_1.bias"))
-            ops.time_embed_rows(t, cat[:, : d.aH], rows // B, d.tmax, ref_bf16=d.time_bf16)
+            ops.time_embed_rows(t, cat[:, : d.aH], rows // B, d.tmax, ref_bf16=d.time_bf16, prefix_len=prefix_len)
             e2 = torch.empty(rows, d.aH, device=dev, dtype=BF16)
             ops.linear(cat, self.w("action_encoder.linear_2.weight"), e2, bias=self.w("action_encoder.linear_2.bias"),
                        epi=PZ_EPI_SILU)
@@ -995,7 +1001,8 @@ class Engine:
         temb = torch.empty(B, d.aH, device=dev, dtype=BF16)
         ops.time_embed(t, temb, d.tmax, ref_bf16=d.time_bf16)
         cat = torch.empty(rows, 2 * d.aH, device=dev, dtype=BF16)
-        ops.concat_time(temb, e1, cat, B, rows // B, d.aH)
+        ops.concat_time(temb, e1, cat, B, rows // B, d.aH, prefix_len=prefix_len, max_period=d.tmax,
+                        ref_bf16=d.time_bf16)
         pre = torch.empty(rows, d.aH, device=dev, dtype=BF16)
         e2 = torch.empty(rows, d.aH, device=dev, dtype=BF16)
         ops.linear(cat, self.w("action_encoder.linear_2.weight"), e2, bias=self.w("action_encoder.linear_2.bias"),
@@ -1448,9 +1455,13 @@ class Engine:
             ops.copy_rows(dX["proprio"], d.aH, 0, dpe, d.aH, 0, 1, B * d.C, d.aH, scale=sa)
             ops.copy_rows(dX["action"], d.aH, 0, de3, d.aH, 0, 1, B * d.H, d.aH, scale=sa)
 
-    def train_forward(self, ids, pix, cnt, pos, proprios, actions, t, x0, save):
-        """pizero.py:607-661: returns fp32 loss [1]; ``save`` collects activations."""
+    def train_forward(self, ids, pix, cnt, pos, proprios, actions, t, x0, save, prefix_len=None):
+        """pizero.py:607-661: returns fp32 loss [1]; ``save`` collects activations.  ``prefix_len`` (int32 [B] on the
+        device): rows h < prefix_len[b] are fed clean (psi = bf16(x1), time 1) and carry no loss; None
+        launches exactly the kernels of a run without the option."""
         d = self.d
+        if d.ada and prefix_len is not None:
+            raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
         dev = pix.device
         B = ids.shape[0]
         tied = self.m._tied
@@ -1461,8 +1472,8 @@ class Engine:
         pe = torch.empty(B * d.C, d.aH, device=dev, dtype=BF16)
         ops.small_linear(prop, self.w("proprio_encoder.weight"), pe, bias=self.w("proprio_encoder.bias"))
         psi = torch.empty(B * d.H, d.A, device=dev, dtype=BF16)
-        ops.flow_psi(x0, actions, t, psi, d.sig_min)
-        e3 = self.action_embed(psi, t, save)
+        ops.flow_psi(x0, actions, t, psi, d.sig_min, prefix_len=prefix_len)
+        e3 = self.action_embed(psi, t, save, prefix_len)
         X = {"vlm": Xv, **self._expert_rows(pe, e3, B, math.sqrt(d.aH))}
         groups = self.groups(tied)
         if d.ada:
@@ -1482,9 +1493,10 @@ class Engine:
         v = torch.empty(B * Tg, 8, device=dev, dtype=BF16)  # columns 0..A-1 written and read (8: 16-B rows)
         ops.small_linear(ya, self.w("action_decoder.weight"), v, bias=self.w("action_decoder.bias"))
         loss = torch.empty(1, device=dev, dtype=F32)
-        ops.flow_loss(v[aoff:], 8, Tg * 8, x0, actions, loss, None, None, B, d.H, d.A, d.sig_min)
+        ops.flow_loss(v[aoff:], 8, Tg * 8, x0, actions, loss, None, None, B, d.H, d.A, d.sig_min,
+                      prefix_len=prefix_len)
         save.update(sv_v=sv_v, ids=ids, cnt=cnt, pos=pos, B=B, prop=prop, pe=pe, Xl=Xl, ya=ya, ra=ra,
-                    x0=x0, x1=actions, v=v, ag=ag, aoff=aoff, Tg=Tg, groups=groups)
+                    x0=x0, x1=actions, v=v, ag=ag, aoff=aoff, Tg=Tg, groups=groups, prefix_len=prefix_len)
         self._chk("train fwd head (action norm, decoder, flow loss)", embed=Xv, ya=ya, v=v, loss=loss)
         return loss
 
@@ -1498,7 +1510,8 @@ class Engine:
         # loss + decoder
         dv = torch.zeros(B * Tg, 8, device=dev, dtype=BF16)
         tmp = torch.empty(1, device=dev, dtype=F32)
-        ops.flow_loss(sv["v"][aoff:], 8, Tg * 8, sv["x0"], sv["x1"], tmp, dv[aoff:], grad_loss, B, d.H, d.A, d.sig_min)
+        ops.flow_loss(sv["v"][aoff:], 8, Tg * 8, sv["x0"], sv["x1"], tmp, dv[aoff:], grad_loss, B, d.H, d.A, d.sig_min,
+                      prefix_len=sv.get("prefix_len"))
         R = B * Tg
         if self.rg("action_decoder.weight"):
             ops.small_gemm(d.A, d.aH, R, dv, 1, 8, sv["ya"], d.aH, 1, self.gw("action_decoder.weight"), d.aH, beta=beta)
@@ -1817,8 +1830,10 @@ class Engine:
             key_split=True)
 
     @_merged_weights
-    def denoise_step(self, action, t, apos, cnt, kcache, vcache, B):
-        """One Euler step of pizero.py:461-481 against the cached vlm+proprio K/V."""
+    def denoise_step(self, action, t, apos, cnt, kcache, vcache, B, prefix_len=None):
+        """One Euler step of pizero.py:461-481 against the cached vlm+proprio K/V.  ``prefix_len`` (int32 [B], DESIGN
+        7f): rows h < prefix_len[b] of ``action`` are embedded with time 1 and not updated, on both glue routes, with
+        the launch count of a step without it."""
         d = self.d
         dev = action.device
         nh, hd, L = d.nh, d.hd, d.L
@@ -1830,7 +1845,7 @@ class Engine:
         if glue:
             cat = torch.empty(B * d.H, 2 * d.aH, device=dev, dtype=BF16)
             ops.action_in(action, self.w("action_encoder.linear_1.weight"), self.w("action_encoder.linear_1.bias"), t,
-                          cat, B, d.H, d.aH, d.tmax, ref_bf16=d.time_bf16)
+                          cat, B, d.H, d.aH, d.tmax, ref_bf16=d.time_bf16, prefix_len=prefix_len)
             sq = math.sqrt(d.aH)
             if sq.is_integer() and (int(sq) & (int(sq) - 1)) == 0:
                 # the joint model's sqrt(hidden) input scaling is a power of two (32 at hidden 1024): folded into the
@@ -1844,7 +1859,7 @@ class Engine:
         else:
             psi = torch.empty(B * d.H, d.A, device=dev, dtype=BF16)
             ops.cast_to_bf16(action, psi)
-            e3 = self.action_embed(psi, t, None)
+            e3 = self.action_embed(psi, t, None, prefix_len)
             x = torch.empty_like(e3)
             ops.copy_rows(e3, d.aH, 0, x, d.aH, 0, 1, B * d.H, d.aH, scale=math.sqrt(d.aH))
         g, = self.groups(self.m._tied, active=("action",))
@@ -1867,13 +1882,13 @@ class Engine:
         if glue:
             ops.action_out(x, self.w("joint_model.mixtures.action.norm.weight"), d.rms_eps,
                            self.w("action_decoder.weight"), self.w("action_decoder.bias"), action, t, B, d.H,
-                           1.0 / d.steps)
+                           1.0 / d.steps, prefix_len=prefix_len)
             return
         y = torch.empty_like(x)
         ops.rmsnorm(x, self.w("joint_model.mixtures.action.norm.weight"), y, None, d.rms_eps)
         v = torch.empty(B * d.H, 8, device=dev, dtype=BF16)
         ops.small_linear(y, self.w("action_decoder.weight"), v[:, : d.A], bias=self.w("action_decoder.bias"))
-        ops.euler_step(action, v, 8, d.H * 8, t, B, d.H, d.A, 1.0 / d.steps)
+        ops.euler_step(action, v, 8, d.H * 8, t, B, d.H, d.A, 1.0 / d.steps, prefix_len=prefix_len)
 
     @_merged_weights
     def denoise_step_ada(self, action, t, Xp, pos, cnt, kcache, vcache, B):
@@ -1925,14 +1940,24 @@ class Engine:
         ops.euler_step(action, v[aoff:], 8, ga.T * 8, t, B, d.H, d.A, 1.0 / d.steps)
 
     @_merged_weights
-    def infer_action(self, ids, pix, cnt, vpos, ppos, apos, proprios, noise, kcache, vcache, clip=True):
+    def infer_action(self, ids, pix, cnt, vpos, ppos, apos, proprios, noise, kcache, vcache, clip=True, prefix=None,
+                     prefix_len=None):
         """pizero.py:416-490.  With an adaLN expert both this and PiZero.infer_action_naive compute the naive
         semantics (pizero.py:492-557): the reference's cached infer_action raises AttributeError there ('NoneType'
         object has no attribute 'ndim' -- its prefill runs the proprio mixture without the time condition), and
-        cannot work, since the proprio K/V depend on t."""
+        cannot work, since the proprio K/V depend on t.
+
+        ``prefix`` (fp32 [B, H, A], normalised action units) with ``prefix_len`` (int32 [B] on the device):
+        rows h < prefix_len[b] of the chunk are the committed actions -- written over the noise before the first step
+        (one launch more per chunk), embedded with time 1, never updated, exempt from the final clamp and returned
+        bit for bit; the other rows are denoised around them.  Neither given: exactly the launches of before."""
         d = self.d
         B = ids.shape[0]
         dev = pix.device
+        if (prefix is None) != (prefix_len is None):
+            raise ValueError("infer_action: prefix and prefix_len go together")
+        if prefix_len is not None and d.ada:
+            raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
         self.fp8_refresh()
         if d.ada:
             self.prefill(ids, pix, cnt, vpos, None, None, kcache, vcache, with_proprio=False)
@@ -1950,12 +1975,16 @@ class Engine:
         else:
             self.prefill(ids, pix, cnt, vpos, ppos, proprios, kcache, vcache)
             step = functools.partial(self.denoise_step, apos=apos)
+            if prefix_len is not None:
+                step = functools.partial(step, prefix_len=prefix_len)
         action = noise.clone()
+        if prefix_len is not None:
+            ops.action_prefix_init(action, prefix, prefix_len)
         t = torch.zeros(B, device=dev, dtype=F32)
         for _ in range(d.steps):
             step(action, t, cnt=cnt, kcache=kcache, vcache=vcache, B=B)
         if clip and d.clip is not None:
-            ops.clamp_(action, -d.clip, d.clip)
+            ops.clamp_(action, -d.clip, d.clip, prefix_len=prefix_len)
         return action
 
     # --------------------------------------------------------------- hooks --

@@ -14,7 +14,42 @@ from __future__ import annotations
 import torch
 
 
+def _prefix_static(static, name):
+    """the two static inputs of a prefix-capable graph: the committed actions and their per-sample count.
+    Both are read by the captured launches, so another delay or prefix replays the same capture."""
+    static[name] = torch.zeros_like(static["noise"])
+    static["prefix_len"] = torch.zeros(static["noise"].shape[0], device=static["noise"].device, dtype=torch.int32)
+
+
+def _load_prefix(static, name, prefix, prefix_len, H, **kw):
+    """copy a prefix into the static inputs; ``prefix_len``: an int or [B] (checked against [0, H - 1] where it lives
+    on the host); neither given: no prefix (prefix_len = 0)"""
+    if name not in static:
+        if prefix is not None or prefix_len is not None:
+            raise ValueError("this graph takes no action prefix: call enable_prefix() before capture()")
+        return
+    if prefix is None or prefix_len is None:
+        if prefix is not None or prefix_len is not None:
+            raise ValueError("the action prefix and its length go together")
+        static["prefix_len"].zero_()
+        return
+    pl = torch.as_tensor(prefix_len)
+    if pl.dtype.is_floating_point or pl.dtype.is_complex or pl.dtype == torch.bool:
+        raise ValueError(f"prefix_len / delay must be integers, got {pl.dtype}")
+    if not pl.is_cuda and (int(pl.min()) < 0 or int(pl.max()) > H - 1):
+        raise ValueError(f"prefix_len / delay must lie in [0, horizon_steps - 1] = [0, {H - 1}], got {pl.tolist()}")
+    static["prefix_len"].copy_(pl.to(torch.int32).expand_as(static["prefix_len"]) if pl.dim() == 0
+                               else pl.reshape(static["prefix_len"].shape), **kw)
+    static[name].copy_(torch.as_tensor(prefix).reshape(static[name].shape), **kw)
+
+
 class InferenceGraph:
+    """After ``enable_prefix()`` the graph also takes a committed action prefix (normalised units) and its
+    per-sample length as static inputs; without that call it is the graph it always was."""
+
+    prefix = False
+    PREFIX_INPUT = "prefix"
+
     def __init__(self, model, bsz, clip=True):
         self.m = model
         self.B = bsz
@@ -37,13 +72,29 @@ class InferenceGraph:
         self.out = None
         self._f8 = None
 
+    def enable_prefix(self):
+        """add the action prefix and its per-sample length to the static inputs (before capture(); a prefix length of
+        0, the state after this call, gives the bits of the graph without the option).  Returns self."""
+        if self.m._engine().d.ada:
+            from .engine import PREFIX_ADAPTIVE_MSG
+
+            raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
+        if not self.prefix:
+            if self.graph is not None:
+                raise RuntimeError("enable_prefix() must precede capture()")
+            _prefix_static(self.static, self.PREFIX_INPUT)
+            self.prefix = True
+        return self
+
     def _run(self):
         s = self.static
         return self.m._engine().infer_action(s["ids"], s["pix"], s["cnt"], s["vpos"], s["ppos"], s["apos"],
-                                              s["proprios"], s["noise"], self.k, self.v, clip=self.clip)
+                                              s["proprios"], s["noise"], self.k, self.v, clip=self.clip,
+                                              prefix=s.get("prefix"), prefix_len=s.get("prefix_len"))
 
-    def load(self, input_ids, pixel_values, cnt, vpos, ppos, apos, proprios, noise):
+    def load(self, input_ids, pixel_values, cnt, vpos, ppos, apos, proprios, noise, prefix=None, prefix_len=None):
         s = self.static
+        _load_prefix(s, "prefix", prefix, prefix_len, s["noise"].shape[1])
         s["ids"].copy_(input_ids)
         s["pix"].copy_(pixel_values.reshape(s["pix"].shape))
         s["cnt"].copy_(cnt)
@@ -95,6 +146,11 @@ class ObservationGraph(InferenceGraph):
       2. ``Engine.infer_action``,
       3. ``pz_action_denormalize`` (the last action dimension, the gripper, passes through).
 
+    ``enable_prefix()`` adds the static inputs ``prev_actions`` (robot units) and ``prefix_len`` and two
+    launches outside the denoise loop, ``pz_action_normalize`` of the previous chunk and the prefix rows written over
+    the noise; the clamp and the denormalisation are replaced by their prefix forms, the latter copying rows
+    ``h < prefix_len[b]`` from ``prev_actions`` bit for bit.
+
     The static inputs are the raw ones; the prefix counts are ``attention_mask.sum(1)``, computed by the caller where
     the mask is born, so no [L, L] mask exists on this path, and the position ids are constants.  ``stats`` is the
     dataset-statistics dict (``proprio`` / ``action`` -> ``p01``, ``p99``, ``mean``, ``std``) with the optional keys
@@ -102,6 +158,8 @@ class ObservationGraph(InferenceGraph):
     capture() and replay() are InferenceGraph's: the weight-refresh and re-capture rules are the same.
     ``run_eager()`` enqueues the same launches without a graph.  ``out`` holds the robot-unit actions and
     ``out_norm`` the model's normalised chunk they were computed from (both fp32 [B, H, A])."""
+
+    PREFIX_INPUT = "prev_actions"  # the previous chunk in ROBOT units: normalised inside the graph, passed through
 
     def __init__(self, model, bsz, frame_hw, stats, channels_last=True, clip=True):
         from . import ops
@@ -151,13 +209,19 @@ class ObservationGraph(InferenceGraph):
         d = self.m._engine().d
         pix = ops.image_resize_norm(s["frames"], d.img, channels_last=self.channels_last)
         proprios = ops.proprio_normalize(s["raw_proprio"], *self.stat["proprio"], self.modes["proprio"])
+        prefix = None
+        if self.prefix:
+            prefix = ops.action_normalize(s["prev_actions"], *self.stat["action"], self.modes["action"], n_pass=1)
         self.out_norm = self.m._engine().infer_action(s["ids"], pix, s["cnt"], s["vpos"], s["ppos"], s["apos"],
-                                                      proprios, s["noise"], self.k, self.v, clip=self.clip)
-        return ops.action_denormalize(self.out_norm, *self.stat["action"], self.modes["action"], n_pass=1)
+                                                      proprios, s["noise"], self.k, self.v, clip=self.clip,
+                                                      prefix=prefix, prefix_len=s.get("prefix_len"))
+        return ops.action_denormalize(self.out_norm, *self.stat["action"], self.modes["action"], n_pass=1,
+                                      prev=s.get("prev_actions"), prefix_len=s.get("prefix_len"))
 
-    def load(self, frames, input_ids, cnt, raw_proprio, noise):
+    def load(self, frames, input_ids, cnt, raw_proprio, noise, prev_actions=None, delay=None):
         s = self.static
         nb = dict(non_blocking=True)
+        _load_prefix(s, "prev_actions", prev_actions, delay, s["noise"].shape[1], **nb)
         s["frames"].copy_(frames.reshape(s["frames"].shape), **nb)
         s["ids"].copy_(input_ids, **nb)
         s["cnt"].copy_(cnt.reshape(s["cnt"].shape), **nb)

@@ -658,14 +658,32 @@ def time_embed(t, out, max_period, ref_bf16=False):
     call("pz_time_embed", _p(t), _p(out), B, D, float(max_period), int(bool(ref_bf16)), _st())
 
 
-def time_embed_rows(t, out, H, max_period, ref_bf16=False):
-    """time embedding of sample r // H into out[r, :] (a column slice of the concat input), B * H rows"""
+def _prefix_len(prefix_len, B):
+    """the int32 [B] device tensor of per-sample prefix lengths the pz_*_prefix entry points read"""
+    assert (prefix_len.dtype == torch.int32 and prefix_len.is_cuda and prefix_len.is_contiguous()
+            and prefix_len.numel() == B), "prefix_len must be a contiguous int32 [B] device tensor"
+    return _p(prefix_len)
+
+
+def time_embed_rows(t, out, H, max_period, ref_bf16=False, prefix_len=None):
+    """time embedding of sample r // H into out[r, :] (a column slice of the concat input), B * H rows; rows
+    h < prefix_len[b] get the embedding of 1.0"""
     rows, D = out.shape
+    if prefix_len is not None:
+        call("pz_time_embed_rows_prefix", _p(t), _p(out), out.stride(0), _prefix_len(prefix_len, rows // H), rows // H,
+             H, D, float(max_period), int(bool(ref_bf16)), _st())
+        return
     call("pz_time_embed_rows", _p(t), _p(out), out.stride(0), rows // H, H, D, float(max_period), int(bool(ref_bf16)),
          _st())
 
 
-def concat_time(temb, e1, out, B, H, D):
+def concat_time(temb, e1, out, B, H, D, prefix_len=None, max_period=None, ref_bf16=False):
+    """out[b*H+h] = [temb[b] | e1[b*H+h]]; with ``prefix_len`` (and the embedding's ``max_period`` / mode) the time
+    columns of rows h < prefix_len[b] are the embedding of 1.0"""
+    if prefix_len is not None:
+        call("pz_concat_time_prefix", _p(temb), _p(e1), _p(out), _prefix_len(prefix_len, B), B, H, D,
+             float(max_period), int(bool(ref_bf16)), _st())
+        return
     call("pz_concat_time", _p(temb), _p(e1), _p(out), B, H, D, _st())
 
 
@@ -673,39 +691,79 @@ def split_time_grad(dcat, de1, rows, D):
     call("pz_split_time_grad", _p(dcat), _p(de1), rows, D, _st())
 
 
-def flow_psi(x0, x1, t, psi, sig_min):
+def flow_psi(x0, x1, t, psi, sig_min, prefix_len=None):
+    """psi = bf16((1 - (1 - sig) t) x0 + t x1) for x0, x1 fp32 [B, H, A]; rows h < prefix_len[b] get bf16(x1)"""
     B = x0.shape[0]
+    if prefix_len is not None:
+        assert x0.dim() == 3, "flow_psi with a prefix needs [B, H, A] inputs"
+        call("pz_flow_psi_prefix", _p(x0), _p(x1), _p(t), _prefix_len(prefix_len, B), _p(psi), B, x0.shape[1],
+             x0.shape[2], float(sig_min), _st())
+        return
     call("pz_flow_psi", _p(x0), _p(x1), _p(t), _p(psi), B, x0[0].numel(), float(sig_min), _st())
 
 
-def flow_loss(v, ldv, vbs, x0, x1, loss, dv, grad_scale, B, H, A, sig_min):
+def flow_loss(v, ldv, vbs, x0, x1, loss, dv, grad_scale, B, H, A, sig_min, prefix_len=None):
+    """mean squared flow error (and its gradient dv); with ``prefix_len`` over the rows h >= prefix_len[b] only, the
+    element count taken from prefix_len on the device"""
+    if prefix_len is not None:
+        call("pz_flow_loss_prefix", _p(v), ldv, vbs, _p(x0), _p(x1), _prefix_len(prefix_len, B), _p(loss), _p(dv),
+             _p(grad_scale), B, H, A, float(sig_min), _st())
+        return
     call("pz_flow_loss", _p(v), ldv, vbs, _p(x0), _p(x1), _p(loss), _p(dv), _p(grad_scale), B, H, A,
          float(sig_min), _st())
 
 
-def action_in(action, W1, b1, t, cat, B, H, D, max_period, ref_bf16=False):
-    """cat[:, :D] = time embedding, cat[:, D:2D] = bf16(action) @ W1^T + b1 (one launch; inference)"""
+def action_in(action, W1, b1, t, cat, B, H, D, max_period, ref_bf16=False, prefix_len=None):
+    """cat[:, :D] = time embedding, cat[:, D:2D] = bf16(action) @ W1^T + b1 (one launch; inference); rows
+    h < prefix_len[b] get the embedding of 1.0"""
     A = action.shape[-1]
+    if prefix_len is not None:
+        call("pz_action_in_prefix", _p(action), A, _p(W1), _p(b1), _p(t), _p(cat), cat.stride(0),
+             _prefix_len(prefix_len, B), B, H, D, float(max_period), int(bool(ref_bf16)), _st())
+        return
     call("pz_action_in", _p(action), A, _p(W1), _p(b1), _p(t), _p(cat), cat.stride(0), B, H, D, float(max_period),
          int(bool(ref_bf16)), _st())
 
 
-def action_out(x, norm_w, eps, Wd, bd, action, t, B, H, dt):
-    """action += dt * (RMSNorm(x) @ Wd^T + bd) (bf16 v), t += dt: the denoise step's tail in one launch"""
+def action_out(x, norm_w, eps, Wd, bd, action, t, B, H, dt, prefix_len=None):
+    """action += dt * (RMSNorm(x) @ Wd^T + bd) (bf16 v), t += dt: the denoise step's tail in one launch; rows
+    h < prefix_len[b] of action are left as they are (t advances all the same)"""
     D = x.shape[1]
+    if prefix_len is not None:
+        call("pz_action_out_prefix", _p(x), x.stride(0), _p(norm_w), float(eps), _p(Wd), _p(bd), D, Wd.shape[0],
+             _p(action), _p(t), _prefix_len(prefix_len, B), B, H, float(dt), _st())
+        return
     call("pz_action_out", _p(x), x.stride(0), _p(norm_w), float(eps), _p(Wd), _p(bd), D, Wd.shape[0], _p(action),
          _p(t), B, H, float(dt), _st())
 
 
-def euler_step(action, v, ldv, vbs, t, B, H, A, dt):
+def euler_step(action, v, ldv, vbs, t, B, H, A, dt, prefix_len=None):
+    if prefix_len is not None:
+        call("pz_euler_step_prefix", _p(action), _p(v), ldv, vbs, _p(t), _prefix_len(prefix_len, B), B, H, A,
+             float(dt), _st())
+        return
     call("pz_euler_step", _p(action), _p(v), ldv, vbs, _p(t), B, H, A, float(dt), _st())
+
+
+def action_prefix_init(action, prefix, prefix_len):
+    """action[b, h, :] = prefix[b, h, :] for h < prefix_len[b] (fp32 [B, H, A], in place; other rows untouched)"""
+    B, H, A = action.shape
+    assert action.dtype == prefix.dtype == torch.float32 and action.is_contiguous() and prefix.is_contiguous()
+    assert prefix.shape == action.shape and prefix.device == action.device
+    call("pz_action_prefix_init", _p(action), _p(prefix), _prefix_len(prefix_len, B), B, H, A, _st())
 
 
 def copy_rows(src, sld, sbs, dst, dld, dbs, B, rows, D, scale=1.0, beta=False):
     call("pz_copy_rows", _p(src), sld, sbs, _p(dst), dld, dbs, B, rows, D, float(scale), int(beta), _st())
 
 
-def clamp_(x, lo, hi):
+def clamp_(x, lo, hi, prefix_len=None):
+    """in-place clamp of fp32 x; with ``prefix_len`` x is [B, H, A] and rows h < prefix_len[b] are exempt"""
+    if prefix_len is not None:
+        B, H, A = x.shape
+        assert x.is_contiguous()
+        call("pz_clamp_prefix", _p(x), _prefix_len(prefix_len, B), B, H, A, float(lo), float(hi), _st())
+        return
     call("pz_clamp", _p(x), x.numel(), float(lo), float(hi), _st())
 
 
@@ -1020,11 +1078,28 @@ def proprio_normalize(x, a, b, mode, out=None):
     return out
 
 
-def action_denormalize(x, a, b, mode, n_pass=1, out=None):
+def action_denormalize(x, a, b, mode, n_pass=1, out=None, prev=None, prefix_len=None):
     """fp32 [..., D] normalised actions -> robot units: "bound" (x + 1) / 2 (b - a) + a, "gaussian" x (b + 1e-8) + a;
-    the trailing ``n_pass`` dimensions (the gripper, simpler.py:105-126) are copied unchanged."""
+    the trailing ``n_pass`` dimensions (the gripper, simpler.py:105-126) are copied unchanged.  With ``prev`` (robot
+    units, x's shape [B, H, D]) and ``prefix_len``, rows h < prefix_len[b] of the result are prev's bits."""
     out, rows, D, m = _norm_args(x, out, a, b, mode)
+    if prefix_len is not None:
+        assert x.dim() == 3 and prev is not None and prev.shape == x.shape and prev.dtype == torch.float32
+        assert prev.is_contiguous() and prev.device == x.device
+        B, H = x.shape[:2]
+        call("pz_action_denormalize_prefix", _p(x), _p(out), _p(prev), _prefix_len(prefix_len, B), B, H, D,
+             int(n_pass), _p(a), _p(b), m, _st())
+        return out
     call("pz_action_denormalize", _p(x), _p(out), rows, D, int(n_pass), _p(a), _p(b), m, _st())
+    return out
+
+
+def action_normalize(x, a, b, mode, n_pass=1, out=None):
+    """the inverse of action_denormalize: fp32 [..., D] robot-unit actions -> the model's normalised actions ("bound":
+    clip(2 (x - a) / (b - a + 1e-8) - 1, -1, 1), "gaussian": (x - a) / (b + 1e-8)); the trailing ``n_pass``
+    dimensions are copied unchanged."""
+    out, rows, D, m = _norm_args(x, out, a, b, mode)
+    call("pz_action_normalize", _p(x), _p(out), rows, D, int(n_pass), _p(a), _p(b), m, _st())
     return out
 
 

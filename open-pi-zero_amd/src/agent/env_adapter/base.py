@@ -64,3 +64,18 @@ class BaseEnvAdapter:
         else:
             raise ValueError(f"action_normalization_type must be one of {NORMALIZATION_TYPES}, got {kind!r}")
         return np.concatenate([head, actions[..., k:]], axis=-1)
+
+    def normalize_action(self, actions, stats, kind="bound", n_pass=1):
+        """the inverse of ``denormalize_action`` (robot units -> the model's action units; the device form is
+        ``pz_action_normalize``): ``normalize_bound`` with its clip, or ``normalize_gaussian``, on every dimension
+        but the trailing ``n_pass``"""
+        s = stats["action"]
+        actions = np.asarray(actions)
+        k = actions.shape[-1] - n_pass
+        if kind == "bound":
+            head = self.normalize_bound(actions[..., :k], np.array(s["p01"])[:k], np.array(s["p99"])[:k])
+        elif kind == "gaussian":
+            head = self.normalize_gaussian(actions[..., :k], np.array(s["mean"])[:k], np.array(s["std"])[:k])
+        else:
+            raise ValueError(f"action_normalization_type must be one of {NORMALIZATION_TYPES}, got {kind!r}")
+        return np.concatenate([head, actions[..., k:]], axis=-1)

@@ -88,19 +88,23 @@ class EvalAgent:
             self._stats = stats
         return self._stats
 
-    def observation_graph(self, bsz, frame_hw, channels_last=True):
-        """the ObservationGraph of one (batch size, frame geometry, layout); built on first use, not yet captured"""
+    def observation_graph(self, bsz, frame_hw, channels_last=True, prefix=False):
+        """the ObservationGraph of one (batch size, frame geometry, layout, with / without an action prefix); built on
+        first use, not yet captured"""
         from pizero_native.graph import ObservationGraph
 
-        key = (bsz, tuple(int(x) for x in frame_hw), bool(channels_last))
+        key = (bsz, tuple(int(x) for x in frame_hw), bool(channels_last)) + ((True,) if prefix else ())
         g = self._obs_graphs.get(key)
         if g is None:
             g = self._obs_graphs[key] = ObservationGraph(self.model, bsz, key[1], self._dataset_statistics(),
                                                          channels_last=channels_last)
+            if prefix:
+                g.enable_prefix()
         return g
 
     @torch.no_grad()
-    def act(self, frames, input_ids, attention_mask, raw_proprio, noise=None, channels_last=True):
+    def act(self, frames, input_ids, attention_mask, raw_proprio, noise=None, channels_last=True, prev_actions=None,
+            delay=None):
         """Raw observation -> fp32 [B, horizon, action_dim] actions in ROBOT units, one graph replay.
 
         ``frames``: uint8 camera frames of any size, [B (* n_images), H, W, 3] (or [.., 3, H, W] with
@@ -109,7 +113,14 @@ class EvalAgent:
         image size, the pixel and proprio normalisation and the action denormalisation run as HIP kernels inside the
         captured graph (``use_graph=False``: the same kernels, enqueued eagerly).  The prefix counts are the
         attention mask's row sums, taken where the mask lives; no [L, L] mask is built.  The returned tensor is the
-        graph's static output: copy it before the next call if it must survive it."""
+        graph's static output: copy it before the next call if it must survive it.
+
+        ``prev_actions`` (robot units, [B, horizon, action_dim]) with ``delay`` (an int or [B], 0 <= delay <
+        horizon): the first ``delay`` actions of the new chunk are the ones the robot executes while this
+        call runs -- ``prev_actions[:, :delay]``, e.g. from ``src.agent.chunking.next_prefix`` -- and the chunk is
+        denoised around them.  Rows >= delay of ``prev_actions`` are ignored.  The returned rows < delay are
+        ``prev_actions``' bits.  One capture serves every delay and prefix; calls without ``prev_actions`` keep
+        using the graph without the option."""
         self._dataset_statistics()  # without statistics: the ValueError that names the key, before anything else
         m = self.model
         frames, input_ids, attention_mask, raw_proprio = (torch.as_tensor(x) for x in
@@ -122,8 +133,21 @@ class EvalAgent:
         cnt = attention_mask.sum(1)
         if noise is None:
             noise = torch.randn(B, m.horizon_steps, m.action_dim, device=self.device)
-        g = self.observation_graph(B, hw, channels_last)
-        g.load(frames.contiguous(), input_ids, cnt, raw_proprio.to(torch.float32), noise)
+        if (prev_actions is None) != (delay is None):
+            raise ValueError("act: prev_actions and delay go together")
+        kw = {}
+        if prev_actions is not None:
+            if m.action_expert_adaptive_mode:
+                from pizero_native.engine import PREFIX_ADAPTIVE_MSG
+
+                raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
+            prev = torch.as_tensor(prev_actions).to(torch.float32)
+            if tuple(prev.shape) != (B, m.horizon_steps, m.action_dim):
+                raise ValueError(f"act: prev_actions must be [B, horizon_steps, action_dim] = "
+                                 f"{(B, m.horizon_steps, m.action_dim)}, got {tuple(prev.shape)}")
+            kw = dict(prev_actions=prev, delay=delay)
+        g = self.observation_graph(B, hw, channels_last, prefix=bool(kw))
+        g.load(frames.contiguous(), input_ids, cnt, raw_proprio.to(torch.float32), noise, **kw)
         if not self.use_graph:
             return g.run_eager()
         if g.graph is None:

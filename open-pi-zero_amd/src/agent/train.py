@@ -25,6 +25,9 @@ agent consumes any iterable of reference-format batches, by default
 ``SyntheticBridgeDataset`` (bridge-shaped random batches, already tokenized).
 What that pipeline does to every training frame after the resize -- random crop and colour jitter
 (src/agent/dataset.py:38-70) -- runs on the device with ``image_augment: True`` (off by default).
+An extension: ``action_prefix_max_delay: D`` > 0 (off by default) trains every sample with its own first
+d ~ U{0..D} actions as a committed, loss-free prefix ("real-time chunking"), so that a chunk can be inferred around
+the actions a robot executes while the inference runs (``EvalAgent.act(prev_actions=, delay=)``).
 """
 
 from __future__ import annotations
@@ -112,6 +115,10 @@ class TrainAgent:
 
         self.cnt_update = 0
         self.cnt_batch = 0
+        # micro-batches consumed so far: cnt_batch in an uninterrupted run.  A checkpoint stores the index of its LAST
+        # micro-batch (the reference's bookkeeping, kept), so load_checkpoint restores cnt_batch + 1 here: what is keyed
+        # on this count (the action-prefix draws) continues across a resume where cnt_batch repeats one index
+        self.micro_batches_seen = 0
         self.wandb_id = None
         self.lora = bool(cfg_get(cfg, "lora", False))
         if cfg_get(cfg, "quantize", False):
@@ -189,6 +196,20 @@ class TrainAgent:
                 raise ValueError(f"image_augment_crop_draws must be one of {list(A.CROP_DRAWS)}, got "
                                  f"{self.image_augment_crop_draws!r}")
 
+        # action-prefix conditioning: off by default (0: nothing is drawn, the step is the one it always
+        # was).  With D > 0 every sample of micro-batch cnt_batch trains with its own first d ~ U{0..D} ground-truth
+        # actions as a committed prefix, d drawn on the host from (action_prefix_seed, micro_batches_seen, rank) alone
+        self.action_prefix_max_delay = int(cfg_get(cfg, "action_prefix_max_delay", 0) or 0)
+        horizon = int(cfg_get(cfg, "horizon_steps"))
+        if not 0 <= self.action_prefix_max_delay < horizon:
+            raise ValueError(f"action_prefix_max_delay must lie in [0, horizon_steps - 1] = [0, {horizon - 1}], got "
+                             f"{self.action_prefix_max_delay}")
+        if self.action_prefix_max_delay and cfg_get(cfg, "action_expert_adaptive_mode", None):
+            from pizero_native.engine import PREFIX_ADAPTIVE_MSG
+
+            raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
+        self.action_prefix_seed = int(cfg_get(cfg, "action_prefix_seed", cfg_get(cfg, "seed", 0)))
+
         # in-training validation (train.py:132-160,413-459): on with a val_dataset or a ``data.val`` config node
         self.run_eval = val_dataset is not None or cfg_get(cfg, "data.val") is not None
         self.last_eval = None
@@ -241,7 +262,29 @@ class TrainAgent:
             inputs["causal_mask"] = mask
         if sample_fm_time:
             inputs["t"] = self.sample_fm_time(len(batch["input_ids"])).to(dev, **nb).to(self.dtype)
+            pl = self._prefix_len(batch)
+            if pl is not None:
+                inputs["prefix_len"] = pl
         return inputs
+
+    def _prefix_len(self, batch):
+        """the training step's per-sample prefix lengths: the batch's own ``action_prefix_len`` if it
+        carries one, else the draw of this micro-batch with ``action_prefix_max_delay`` > 0, else None"""
+        bsz = len(batch["input_ids"])
+        if batch.get("action_prefix_len") is not None:
+            pl = torch.as_tensor(batch["action_prefix_len"])
+        elif self.action_prefix_max_delay > 0:
+            from pizero_native import augment as A
+
+            pl = torch.from_numpy(A.draw_prefix_len(bsz, self.action_prefix_max_delay, self.action_prefix_seed,
+                                                    self.micro_batches_seen, self.rank))
+        else:
+            return None
+        horizon = int(cfg_get(self.cfg, "horizon_steps"))
+        if pl.numel() != bsz or int(pl.min()) < 0 or int(pl.max()) > horizon - 1:
+            raise ValueError(f"action_prefix_len: {bsz} integers in [0, horizon_steps - 1] = [0, {horizon - 1}] "
+                             f"expected, got {pl.tolist()}")
+        return pl.to(torch.int32)
 
     def _augment_frames(self, pix, img):
         """uint8 [B, 3, H, W] on the device -> bf16 [B, 3, img, img]: the resize first where the frames are not at the
@@ -306,6 +349,7 @@ class TrainAgent:
                     log.info("Batch %d Update %d: loss %.4f | action lr %.8f", self.cnt_batch, self.cnt_update,
                              float(win.mean()), self.action_optimizer.param_groups[0]["lr"])
             self.cnt_batch += 1
+            self.micro_batches_seen += 1
         return self
 
     # ----------------------------------------------------------- validation --
@@ -323,29 +367,46 @@ class TrainAgent:
             self.val_dataiterator = iter(self.val_dataloader)
         acc = torch.zeros(len(self.eval_thresholds), device=self.device)
         l1 = torch.tensor(0.0, device=self.device)
+        D = self.action_prefix_max_delay
+        l1_suffix = torch.tensor(0.0, device=self.device)
         self.model_meta.eval()
         try:
             with self.model_averaging.averaged_weights() as model_eval, torch.no_grad():
                 for _ in range(n):
                     inputs = self.preprocess_batch(next(self.val_dataiterator), split_mask=True, sample_fm_time=False)
                     gt_actions = inputs.pop("actions")
+                    if D > 0:  # infer_action's own draw, made here so that both chunks start from the same noise
+                        inputs["noise"] = torch.randn(gt_actions.shape, device=self.device, dtype=torch.float32)
                     preds = model_eval.infer_action(**inputs)
                     acc += get_action_accuracy(gt_actions, preds, self.eval_thresholds)
                     l1 += torch.nn.functional.l1_loss(preds, gt_actions)
+                    if D > 0:  # the chunk again around its ground-truth first D actions: L1 over the rows it fills in
+                        cond = model_eval.infer_action(**inputs, prefix_actions=gt_actions.float(),
+                                                       prefix_len=torch.full((len(gt_actions),), D))
+                        l1_suffix += torch.nn.functional.l1_loss(cond[:, D:], gt_actions[:, D:].float())
         finally:
             self.model_meta.train()
         acc /= n
         l1 /= n
+        l1_suffix /= n
         if self.multi_gpu:
             torch.distributed.all_reduce(acc, op=torch.distributed.ReduceOp.SUM)
             torch.distributed.all_reduce(l1, op=torch.distributed.ReduceOp.SUM)
             acc /= self.world
             l1 /= self.world
+            if D > 0:
+                torch.distributed.all_reduce(l1_suffix, op=torch.distributed.ReduceOp.SUM)
+                l1_suffix /= self.world
         self.last_eval = {"l1": float(l1), "accuracy": [float(x) for x in acc], "cnt_batch": int(self.cnt_batch)}
+        if D > 0:
+            self.last_eval["l1_prefix_suffix"] = float(l1_suffix)
         if self.main_rank:
             log.info("Eval | l1 Loss: %.3f | %s", self.last_eval["l1"],
                      " | ".join(f"acc thres {t}: {a:.3f}" for t, a in zip(self.eval_thresholds,
                                                                           self.last_eval["accuracy"])))
+            if D > 0:
+                log.info("Eval | l1 Loss over rows >= %d around the ground-truth first %d actions: %.3f", D, D,
+                         self.last_eval["l1_prefix_suffix"])
         return self.last_eval
 
     # ---------------------------------------------------------- checkpoints --
@@ -379,6 +440,7 @@ class TrainAgent:
         data = torch.load(path, weights_only=True, map_location="cpu")
         self.cnt_update = int(data["cnt_update"])
         self.cnt_batch = int(data["cnt_batch"])
+        self.micro_batches_seen = self.cnt_batch + 1  # the checkpoint was written after micro-batch cnt_batch
         self.wandb_id = data.get("wandb_id")
         sd = {k.replace("_orig_mod.", ""): v for k, v in data["model"].items()}
         if self._averaging_enabled and data.get("model_train") is not None:

@@ -576,8 +576,11 @@ class PiZero(nn.Module, NoSyncBase):
         return (1 - (1 - self.flow_sig_min) * t) * x + t * x1
 
     def forward(self, input_ids, pixel_values, causal_mask, vlm_position_ids, proprio_position_ids,
-                action_position_ids, proprios, actions, t, noise: Optional[torch.Tensor] = None):
-        """Flow-matching loss (pizero.py:607-661); ``noise`` = x0 (default torch.randn_like)."""
+                action_position_ids, proprios, actions, t, noise: Optional[torch.Tensor] = None,
+                prefix_len: Optional[torch.Tensor] = None):
+        """Flow-matching loss (pizero.py:607-661); ``noise`` = x0 (default torch.randn_like).  ``prefix_len`` (ints
+        [B]): the first prefix_len[b] actions of sample b are a committed prefix -- fed clean with flow
+        time 1, given no loss, attended to by the rest.  None: today's loss, with today's kernels."""
         dev = self._dev()
         cdt = self._arena.data.dtype
         if cdt != torch.bfloat16:
@@ -597,6 +600,8 @@ class PiZero(nn.Module, NoSyncBase):
                      cnt=self._mask_spec([cm], [torch.arange(cm.shape[2], device=dev)]), pos=pos,
                      proprios=proprios.to(dev, torch.float32).contiguous(), actions=x1,
                      t=t.to(dev, torch.float32).contiguous(), x0=x0)
+        if prefix_len is not None:
+            batch["prefix_len"] = self._prefix_len(prefix_len, x1.shape[0])
         anchor = next((self._param(n) for n in self._trainable_names()), None)
         if anchor is not None and torch.is_grad_enabled():
             self._check_ddp_wrapper()
@@ -604,6 +609,25 @@ class PiZero(nn.Module, NoSyncBase):
             save = {}
             return self._engine().train_forward(save=save, **batch).view(())
         return _PiZeroLoss.apply(anchor, self, batch)
+
+    def _prefix_len(self, prefix_len, B):
+        """ints [B] (or one int) -> the int32 [B] device tensor the engine takes; refused with an adaLN expert, and
+        outside [0, horizon_steps - 1] where the values are known on the host"""
+        if self.action_expert_adaptive_mode:
+            from pizero_native.engine import PREFIX_ADAPTIVE_MSG
+
+            raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
+        pl = torch.as_tensor(prefix_len)
+        if pl.dtype.is_floating_point or pl.dtype.is_complex or pl.dtype == torch.bool:
+            raise ValueError(f"prefix_len must be integers, got {pl.dtype}")
+        if pl.dim() == 0:
+            pl = pl.expand(B)
+        if pl.numel() != B:
+            raise ValueError(f"prefix_len has {pl.numel()} entries for a batch of {B}")
+        H = self.horizon_steps
+        if not pl.is_cuda and pl.numel() and (int(pl.min()) < 0 or int(pl.max()) > H - 1):
+            raise ValueError(f"prefix_len must lie in [0, horizon_steps - 1] = [0, {H - 1}], got {pl.tolist()}")
+        return pl.reshape(B).to(self._dev(), torch.int32).contiguous()
 
     def _check_ddp_wrapper(self):
         """torch DDP (train.py:121-126) cannot reduce this model's gradients: the native backward writes
@@ -632,12 +656,18 @@ class PiZero(nn.Module, NoSyncBase):
     @torch.no_grad()
     def infer_action(self, input_ids, pixel_values, image_text_proprio_mask, action_mask, vlm_position_ids,
                      proprio_position_ids, action_position_ids, proprios, noise: Optional[torch.Tensor] = None,
-                     clip: bool = True):
+                     clip: bool = True, prefix_actions: Optional[torch.Tensor] = None,
+                     prefix_len: Optional[torch.Tensor] = None):
         """pizero.py:416-490: prefill caches vlm+proprio K/V once, 10 Euler steps on the action expert.
+        ``prefix_actions`` [B, horizon, action_dim] (normalised units) with ``prefix_len`` (ints [B]): the
+        first prefix_len[b] actions of the chunk are committed -- returned bit for bit (fp32), the rest denoised
+        around them; rows of ``prefix_actions`` past prefix_len[b] are ignored.
         With an adaLN expert (action_expert_adaptive_mode) the reference's cached path raises AttributeError
         ('NoneType' object has no attribute 'ndim': its prefill runs the proprio mixture without the time condition)
         and cannot work, since the proprio K/V depend on t: here it computes infer_action_naive's result -- the vlm
         K/V cached once, the proprio + action rows re-run with cond(t) every Euler step."""
+        if (prefix_actions is None) != (prefix_len is None):
+            raise ValueError("infer_action: prefix_actions and prefix_len go together")
         dev = self._dev()
         B = input_ids.shape[0]
         dtype = pixel_values.dtype
@@ -648,21 +678,33 @@ class PiZero(nn.Module, NoSyncBase):
         L1 = itp.shape[2]
         spec = self._mask_spec([itp, am], [torch.arange(L1, device=dev),
                                            torch.arange(L1, L1 + am.shape[2], device=dev)])
+        kw = {}
+        if prefix_len is not None:
+            pa = torch.as_tensor(prefix_actions).to(dev, torch.float32).contiguous()
+            if tuple(pa.shape) != (B, self.horizon_steps, self.action_dim):
+                raise ValueError(f"prefix_actions must be [B, horizon_steps, action_dim] = "
+                                 f"{(B, self.horizon_steps, self.action_dim)}, got {tuple(pa.shape)}")
+            kw = dict(prefix=pa, prefix_len=self._prefix_len(prefix_len, B))
+            dtype = torch.float32  # the committed rows come back bit for bit
         a = self._engine().infer_action(
             input_ids.to(dev, torch.int64).contiguous(), pixel_values.to(dev, torch.bfloat16).contiguous(),
             spec, vlm_position_ids.to(dev, torch.int64).contiguous(),
             proprio_position_ids.to(dev, torch.int64).contiguous(), action_position_ids.to(dev, torch.int64).contiguous(),
             proprios.to(dev, torch.float32).contiguous(), noise.to(dev, torch.float32).contiguous(), k, v,
-            clip=clip and self.final_action_clip_value is not None)
+            clip=clip and self.final_action_clip_value is not None, **kw)
         return a.to(dtype)
 
     @torch.no_grad()
     def infer_action_naive(self, input_ids, pixel_values, causal_mask, vlm_position_ids, proprio_position_ids,
-                           action_position_ids, proprios, noise: Optional[torch.Tensor] = None, clip: bool = True):
+                           action_position_ids, proprios, noise: Optional[torch.Tensor] = None, clip: bool = True,
+                           prefix_actions=None, prefix_len=None):
         """pizero.py:492-557.  Re-running the prefix every step gives identical math (the vlm/proprio rows
         never attend to actions), so the native path reuses the cached prefix (fp32-exact equivalence:
         SURVEY 8(c) measured |naive - cached| = 1.8e-7).  With an adaLN expert only the vlm rows are cached: the
         proprio rows depend on t and are re-run with the action rows in every Euler step (see infer_action)."""
+        if prefix_actions is not None or prefix_len is not None:
+            raise NotImplementedError("infer_action_naive takes no action prefix (prefix_actions / prefix_len, DESIGN "
+                                      "7f): use infer_action")
         itp, amask = self.split_full_mask_into_submasks(causal_mask)
         return self.infer_action(input_ids, pixel_values, itp, amask, vlm_position_ids, proprio_position_ids,
                                  action_position_ids, proprios, noise=noise, clip=clip)
@@ -729,6 +771,8 @@ class PiZero(nn.Module, NoSyncBase):
 
 class PiZeroInference(PiZero):
     def forward(self, input_ids, pixel_values, image_text_proprio_mask, action_mask, vlm_position_ids,
-                proprio_position_ids, action_position_ids, proprios, noise=None):
+                proprio_position_ids, action_position_ids, proprios, noise=None, prefix_actions=None,
+                prefix_len=None):
         return super().infer_action(input_ids, pixel_values, image_text_proprio_mask, action_mask,
-                                    vlm_position_ids, proprio_position_ids, action_position_ids, proprios, noise=noise)
+                                    vlm_position_ids, proprio_position_ids, action_position_ids, proprios, noise=noise,
+                                    prefix_actions=prefix_actions, prefix_len=prefix_len)
