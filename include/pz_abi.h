@@ -617,6 +617,34 @@ int pz_image_resize_u8(const void* frames, int32_t channels_last, int64_t n, int
                        const void* v_count, const void* v_w, int64_t v_taps, void* scratch, int64_t scratch_bytes,
                        void* out, void* stream);
 
+/* Micro-batch assembly from an episode store in device memory (csrc/pz_episodes.hip).  Entry points added
+ * under ABI 22 (no existing signature changed).  Both kernels only move bytes: no atomics, no LDS.
+ *
+ * pz_episode_gather_frames: store uint8 [N, C, H, W, 3] (C cameras, channels last), idx int64 [B] frame rows (device
+ *   memory) -> out uint8 [B * C, 3, H, W], the layout pz_image_resize_* and pz_image_augment take with
+ *   channels_last = 0: out unit b * C + c is store unit idx[b] * C + c with its three channels separated.  idx = null
+ *   is the identity (unit u of a [B, C, H, W, 3] staging buffer -> out unit u; needs B <= N).  With H * W % 16 == 0 and
+ *   16-byte aligned store / out every lane moves 16 pixels (three 16-byte loads, byte permutes, three 16-byte planar
+ *   stores); any other geometry or alignment moves bytes.  A row outside [0, N) is skipped (its outputs are not
+ *   written); callers check the rows on the host.
+ * pz_episode_gather_rows: for sample b at step t = idx[b] of episode e = episode_of[t] (int32 [N]), whose rows are
+ *   [s, en) = episode_offsets[e], episode_offsets[e + 1] (int64 [E + 1]):
+ *     out_action fp32 [B, H, A]      = action[min(t + h, en - 1)]          (the last action repeated)
+ *     out_proprio fp32 [B, W, P]     = proprio[max(t - W + 1 + w, s)]      (the first step repeated)
+ *     out_pad_mask uint8 [B, H]      = t + h <= en - 1
+ *     out_input_ids int64 [B, L]     = tokens[e] (int32 [E, L]);  out_attention_mask int64 [B, L] = ids != pad_id
+ *   action fp32 [N, A] and proprio fp32 [N, P] are gathered as they are (normalise them once, beforehand).  A sample
+ *   whose t, e or episode bounds are out of range is skipped.
+ * PZ_ERR_INVALID_ARG before any launch for null pointers, non-positive dimensions, dimensions above
+ * PZ_OBS_MAX_EXTENT (C above 64), misaligned pointers, or more elements than one launch addresses. */
+int pz_episode_gather_frames(const void* store, int64_t N, int64_t C, int64_t H, int64_t W, const void* idx, int64_t B,
+                             void* out, void* stream);
+int pz_episode_gather_rows(const void* action, const void* proprio, const void* episode_of,
+                           const void* episode_offsets, const void* tokens, const void* idx, int64_t N, int64_t E,
+                           int64_t A, int64_t P, int64_t L, int64_t B, int64_t W, int64_t H, int32_t pad_id,
+                           void* out_action, void* out_proprio, void* out_pad_mask, void* out_input_ids,
+                           void* out_attention_mask, void* stream);
+
 /* test instrument: fill every CU's LDS with `word` (0xffffffff = NaN) on `stream`, so the next kernel's reads of
  * LDS it did not write return NaN (tests/test_train_loop_gpu.py; _lib.call runs it before every launch under
  * PZ_POISON_LDS=1).  Not on any product path. */

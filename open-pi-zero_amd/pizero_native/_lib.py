@@ -212,6 +212,10 @@ SIGNATURES = {
     "pz_image_augment_scratch_bytes": [i64, i64],
     "pz_image_augment": [vp, i32, i64, i64, vp, vp, i32, vp, vp, i64, vp, vp],
     "pz_image_resize_u8": [vp, i32, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp],
+    # micro-batch assembly from an episode store
+    "pz_episode_gather_frames": [vp, i64, i64, i64, i64, vp, i64, vp, vp],
+    "pz_episode_gather_rows": [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp,
+                               vp],
     "pz_debug_poison_lds": [C.c_uint32, vp],
     "pz_debug_spin": [i64, i64, vp],
     "pz_last_error": [],

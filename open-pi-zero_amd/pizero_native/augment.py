@@ -134,6 +134,9 @@ def generator(seed, cnt_batch, rank, stream=0):
 
 
 PREFIX_STREAM = 0x7072656669785F64  # "prefix_d": the action-prefix delays' stream
+# the episode sampler's epoch permutations (pizero_native.episodes): training and validation
+EPISODE_STREAM = 0x657069736F646573  # "episodes"
+EPISODE_VAL_STREAM = 0x657069735F76616C  # "epis_val"
 
 
 def draw_prefix_len(bsz, max_delay, seed, cnt_batch, rank=0):

@@ -1103,6 +1103,108 @@ def action_normalize(x, a, b, mode, n_pass=1, out=None):
     return out
 
 
+# ---- micro-batch assembly from an episode store (csrc/pz_episodes.hip) ----------------------------------
+def _episode_idx(who, idx, n_rows):
+    """the host's check of the sample rows: int64 numpy [B], every row in [0, n_rows) -- before anything is uploaded"""
+    import numpy as np
+
+    if not isinstance(idx, np.ndarray) or idx.dtype != np.int64 or idx.ndim != 1 or idx.size < 1:
+        raise ValueError(f"{who}: idx must be a non-empty one-dimensional int64 numpy array on the host, got "
+                         f"{type(idx).__name__} {getattr(idx, 'dtype', '')} {getattr(idx, 'shape', '')}")
+    lo, hi = int(idx.min()), int(idx.max())
+    if lo < 0 or hi >= n_rows:
+        raise ValueError(f"{who}: idx must lie in [0, {n_rows}), got values from {lo} to {hi}")
+    return np.ascontiguousarray(idx)
+
+
+def _episode_tensor(who, name, t, dtype, shape=None, ndim=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor, got "
+                         f"{getattr(t, 'dtype', type(t).__name__)}")
+    if ndim is not None and t.dim() != ndim:
+        raise ValueError(f"{who}: {name} must have {ndim} dimensions, got shape {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _episode_on_device(who, dev, **tensors):
+    for name, t in tensors.items():
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"{who}: {name} must be in the memory of {dev}, it is on {t.device}")
+
+
+def episode_gather_frames(store, idx=None, out=None):
+    """uint8 store [N, C, H, W, 3] in device memory, frame rows ``idx`` (int64 numpy [B] on the host, checked against
+    [0, N) here, before anything is uploaded or launched) -> uint8 [B * C, 3, H, W]: frame b * C + c is camera c of row
+    idx[b], channels first, as image_resize_* / image_augment / TrainAgent.preprocess_batch take it.  ``idx=None`` is
+    the identity: the store is a [B, C, H, W, 3] staging buffer that is already gathered."""
+    who = "episode_gather_frames"
+    _episode_tensor(who, "store", store, torch.uint8, ndim=5)
+    N, Cn, H, W, ch = store.shape
+    if ch != 3 or N < 1 or Cn < 1 or H < 1 or W < 1:
+        raise ValueError(f"{who}: store must be [N, C, H, W, 3] with positive sizes, got {tuple(store.shape)}")
+    if idx is None:
+        B, host_idx = N, None
+    else:
+        host_idx = _episode_idx(who, idx, N)
+        B = host_idx.size
+    if out is not None:
+        _episode_tensor(who, "out", out, torch.uint8, shape=(B * Cn, 3, H, W))
+    _episode_on_device(who, store.device, store=store, **({"out": out} if out is not None else {}))
+    if out is None:
+        out = torch.empty(B * Cn, 3, H, W, device=store.device, dtype=torch.uint8)
+    dev_idx = None if host_idx is None else torch.from_numpy(host_idx).to(store.device)
+    call("pz_episode_gather_frames", _p(store), N, Cn, H, W, _p(dev_idx), B, _p(out), _st())
+    return out
+
+
+def episode_gather_rows(action, proprio, episode_of, episode_offsets, tokens, idx, window, horizon, pad_id, out=None):
+    """One launch for everything of a micro-batch but its frames.  Device tensors: ``action`` fp32 [N, A] and
+    ``proprio`` fp32 [N, P] (already normalised: the kernel gathers only), ``episode_of`` int32 [N], ``episode_offsets``
+    int64 [E + 1], ``tokens`` int32 [E, L]; ``idx`` int64 numpy [B] on the host (checked against [0, N) here).  Returns
+    {"action": fp32 [B, horizon, A], "proprio": fp32 [B, window, P], "action_pad_mask": uint8 [B, horizon],
+    "input_ids": int64 [B, L], "attention_mask": int64 [B, L]}: sample b is step t = idx[b] of its episode [s, e): action
+    rows min(t + h, e - 1), proprio rows max(t - window + 1 + w, s), pad mask t + h <= e - 1, the episode's tokens and
+    ids != pad_id.  ``out`` may hold preallocated tensors under those names (exact shapes)."""
+    who = "episode_gather_rows"
+    _episode_tensor(who, "action", action, torch.float32, ndim=2)
+    _episode_tensor(who, "proprio", proprio, torch.float32, ndim=2)
+    N, A = action.shape
+    P = proprio.shape[1]
+    _episode_tensor(who, "proprio", proprio, torch.float32, shape=(N, P))
+    _episode_tensor(who, "episode_of", episode_of, torch.int32, shape=(N,))
+    _episode_tensor(who, "episode_offsets", episode_offsets, torch.int64, ndim=1)
+    _episode_tensor(who, "tokens", tokens, torch.int32, ndim=2)
+    E, L = tokens.shape
+    if episode_offsets.numel() != E + 1 or E < 1 or N < 1 or A < 1 or P < 1 or L < 1:
+        raise ValueError(f"{who}: episode_offsets must have E + 1 = {E + 1} entries and every size be positive, got "
+                         f"{episode_offsets.numel()} offsets, N {N}, A {A}, P {P}, L {L}")
+    Wn, Hn = int(window), int(horizon)
+    if Wn < 1 or Hn < 1:
+        raise ValueError(f"{who}: window and horizon must be positive, got {window}, {horizon}")
+    host_idx = _episode_idx(who, idx, N)
+    B = host_idx.size
+    shapes = {"action": ((B, Hn, A), torch.float32), "proprio": ((B, Wn, P), torch.float32),
+              "action_pad_mask": ((B, Hn), torch.uint8), "input_ids": ((B, L), torch.int64),
+              "attention_mask": ((B, L), torch.int64)}
+    dev = action.device
+    if out is not None:
+        if set(out) != set(shapes):
+            raise ValueError(f"{who}: out must hold exactly {sorted(shapes)}, got {sorted(out)}")
+        for k, (shape, dt) in shapes.items():
+            _episode_tensor(who, f"out[{k!r}]", out[k], dt, shape=shape)
+    _episode_on_device(who, dev, action=action, proprio=proprio, episode_of=episode_of,
+                       episode_offsets=episode_offsets, tokens=tokens,
+                       **({f"out_{k}": v for k, v in out.items()} if out is not None else {}))
+    if out is None:
+        out = {k: torch.empty(shape, device=dev, dtype=dt) for k, (shape, dt) in shapes.items()}
+    dev_idx = torch.from_numpy(host_idx).to(dev)
+    call("pz_episode_gather_rows", _p(action), _p(proprio), _p(episode_of), _p(episode_offsets), _p(tokens),
+         _p(dev_idx), N, E, A, P, L, B, Wn, Hn, int(pad_id), _p(out["action"]), _p(out["proprio"]),
+         _p(out["action_pad_mask"]), _p(out["input_ids"]), _p(out["attention_mask"]), _st())
+    return out
+
+
 def debug_poison_lds(word=0xFFFFFFFF):
     """Test instrument: fill every CU's LDS with ``word`` (0xffffffff = NaN) on the current stream."""
     call("pz_debug_poison_lds", C.c_uint32(int(word) & 0xFFFFFFFF), _st())

@@ -23,6 +23,8 @@ optimizer state dicts, so a resumed run continues bit for bit.
 Data: the OXE/RLDS TensorFlow pipeline is out of scope; the
 agent consumes any iterable of reference-format batches, by default
 ``SyntheticBridgeDataset`` (bridge-shaped random batches, already tokenized).
+With ``data.train.episode_store`` (``data.val.episode_store``) set and no dataset handed in, the batches come from an
+episode store instead, chunked, normalised and assembled on the device (pizero_native.episodes).
 What that pipeline does to every training frame after the resize -- random crop and colour jitter
 (src/agent/dataset.py:38-70) -- runs on the device with ``image_augment: True`` (off by default).
 An extension: ``action_prefix_max_delay: D`` > 0 (off by default) trains every sample with its own first
@@ -147,6 +149,10 @@ class TrainAgent:
 
         per_dev = int(cfg_get(cfg, "per_device_batch_size"))
         self.grad_accumulation_steps = max(int(cfg_get(cfg, "global_batch_size")) // per_dev // self.world, 1)
+        # batches assembled on the device from an episode store (``data.train.episode_store``), when no
+        # dataset is handed in; without the key, the synthetic batches as before
+        if dataset is None:
+            dataset = self._episode_batches("train", per_dev)
         self.train_dataloader = dataset if dataset is not None else SyntheticBridgeDataset(cfg, per_dev, seed=self.rank)
 
         self.train_vlm = bool(cfg_get(cfg, "train_vlm", True))
@@ -219,9 +225,19 @@ class TrainAgent:
             self.per_device_num_eval_batch = int(cfg_get(cfg, "eval_size", 1024)) // per_dev // self.world
             if self.per_device_num_eval_batch < 1:
                 raise ValueError("eval_size is smaller than one batch per rank (per_device_batch_size x world size)")
+            if val_dataset is None:
+                val_dataset = self._episode_batches("val", per_dev)
             self.val_dataloader = (val_dataset if val_dataset is not None
                                    else SyntheticBridgeDataset(cfg, per_dev, seed=10_000 + self.rank))
             self.val_dataiterator = None
+
+    def _episode_batches(self, split, per_dev):
+        """``data.<split>.episode_store`` -> pizero_native.episodes.EpisodeBatches (None without the key)"""
+        if not cfg_get(self.cfg, f"data.{split}.episode_store"):
+            return None
+        from pizero_native.episodes import from_config
+
+        return from_config(self.cfg, split, per_dev, self.rank, self.world, self.device)
 
     def sample_fm_time(self, bsz):
         """train.py:239-247."""
@@ -306,10 +322,20 @@ class TrainAgent:
         return ops.image_augment(pix, params, op_mask, channels_last=False)
 
     def run(self):
+        try:
+            return self._run()
+        finally:  # an episode store's prefetch worker is joined however the loop ends
+            for data in (self.train_dataloader, getattr(self, "val_dataloader", None)):
+                if hasattr(data, "seek") and hasattr(data, "close"):
+                    data.close()
+
+    def _run(self):
         from pizero_native.optim import clip_grad_norm_
 
         loss_deque = deque(maxlen=self.grad_accumulation_steps)
         self.model_meta.train()
+        if hasattr(self.train_dataloader, "seek"):  # a resumed run continues the sampler's sequence
+            self.train_dataloader.seek(self.micro_batches_seen)
         it = iter(self.train_dataloader)
         while self.cnt_update < self.n_updates:
             batch = next(it)
