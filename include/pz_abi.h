@@ -329,6 +329,33 @@ typedef struct pz_decode_attn_args {
 int64_t pz_decode_attn_ws_bytes(int64_t B, int64_t rows, int64_t nk);
 int pz_decode_attn(const pz_decode_attn_args* a, void* stream);
 
+/* Training attention of the action expert against a forward-only VLM (train_vlm: False).
+ * pz_expert_attn_fwd: exactly pz_decode_attn (same arguments, addressing, workspace and O bits) that also writes the
+ * fp32 log-sum-exp of the capped, masked logits of every query row, lse[b*T*nh + t*nh + h].
+ * pz_expert_attn_bwd: from the forward's q / k / v / geometry / mask, its O and lse, and dO bf16
+ * [(b*T + t)*lddo + h*256 ..]: p = exp(cap*t - lse), t = tanh(scale*q.k/cap), delta = rowsum(dO*O),
+ * dS = scale*(1 - t^2)*p*(dO.V^T - delta); dq = dS K addressed like q (bf16); dk_j = sum_r dS[r,j] q_r and
+ * dv_j = sum_r p[r,j] dO_r over all tokens and heads for key rows [key0, key0 + nkeys) only, at
+ * dk + b*dk_bstride + (j - key0)*256 (bf16); no other row of dk / dv is written.  Products on the MFMA, fp32 partials
+ * (dq per key-chunk group, dk / dv per 32-row tile) in ws (pz_expert_attn_bwd_ws_bytes(B, T*nh, nk, nkeys)), merged in
+ * fixed order: deterministic, no atomics.  head_dim 256, T*nh <= 1024. */
+typedef struct pz_expert_attn_bwd_args {
+  const void* q; int64_t ldq, Lq, qoff;
+  const void* k; const void* v; int64_t k_bstride, v_bstride;
+  const void* o; int64_t ldo;
+  const void* dO; int64_t lddo;
+  const float* lse;
+  int64_t B, nh, T, nk, head_dim;
+  float scale, cap;
+  const int32_t* cnt; int64_t prefix, cond, qtok0;
+  void* dq;
+  void* dk; void* dv; int64_t dk_bstride, dv_bstride, key0, nkeys;
+  float* ws; int64_t ws_bytes;
+} pz_expert_attn_bwd_args;
+int pz_expert_attn_fwd(const pz_decode_attn_args* a, float* lse, void* stream);
+int64_t pz_expert_attn_bwd_ws_bytes(int64_t B, int64_t rows, int64_t nk, int64_t nkeys);
+int pz_expert_attn_bwd(const pz_expert_attn_bwd_args* a, void* stream);
+
 /* SigLIP patch embed im2col (siglip.py:42-48,69-74): pixels bf16 [B,3,H,W] -> cols bf16
  * [B*(H/ps)*(W/ps), ldc] with k = c*ps*ps + ky*ps + kx, zero pad k in [3*ps*ps, ldc) */
 int pz_patchify(const void* pix, void* cols, int64_t B, int64_t H, int64_t W, int64_t ps, int64_t ldc,

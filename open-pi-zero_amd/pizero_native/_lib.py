@@ -124,6 +124,16 @@ class DecodeAttnArgs(C.Structure):
     ]
 
 
+class ExpertAttnBwdArgs(C.Structure):
+    _fields_ = [
+        ("q", vp), ("ldq", i64), ("Lq", i64), ("qoff", i64), ("k", vp), ("v", vp), ("k_bstride", i64),
+        ("v_bstride", i64), ("o", vp), ("ldo", i64), ("dO", vp), ("lddo", i64), ("lse", vp), ("B", i64), ("nh", i64),
+        ("T", i64), ("nk", i64), ("head_dim", i64), ("scale", f32), ("cap", f32), ("cnt", vp), ("prefix", i64),
+        ("cond", i64), ("qtok0", i64), ("dq", vp), ("dk", vp), ("dv", vp), ("dk_bstride", i64), ("dv_bstride", i64),
+        ("key0", i64), ("nkeys", i64), ("ws", vp), ("ws_bytes", i64),
+    ]
+
+
 # name -> argtypes (restype int unless listed in _RESTYPE)
 SIGNATURES = {
     "pz_gemm": [C.POINTER(GemmArgs), vp],
@@ -154,6 +164,9 @@ SIGNATURES = {
     "pz_gemm_qkv_rope": [C.POINTER(QkvRopeArgs), vp],
     "pz_decode_attn": [C.POINTER(DecodeAttnArgs), vp],
     "pz_decode_attn_ws_bytes": [i64, i64, i64],
+    "pz_expert_attn_fwd": [C.POINTER(DecodeAttnArgs), vp, vp],
+    "pz_expert_attn_bwd_ws_bytes": [i64, i64, i64, i64],
+    "pz_expert_attn_bwd": [C.POINTER(ExpertAttnBwdArgs), vp],
     "pz_attn_softmax": [C.POINTER(SoftmaxArgs), vp],
     "pz_attn_softmax_bwd": [vp, vp, i64, vp, vp, i64, i64, i64, f32, f32, vp],
     "pz_flash_fwd": [C.POINTER(FlashArgs), vp],
@@ -223,7 +236,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"pz_last_error": C.c_char_p, "pz_gemm_kernel_name": C.c_char_p, "pz_norm_rows_per_part": i64,
             "pz_decode_attn_ws_bytes": i64, "pz_lora_wgrad_ws_bytes": i64, "pz_image_resize_scratch_bytes": i64,
-            "pz_image_augment_scratch_bytes": i64}
+            "pz_image_augment_scratch_bytes": i64, "pz_expert_attn_bwd_ws_bytes": i64}
 
 _lib = None
 
@@ -254,7 +267,7 @@ def lib():
 # entry points that enqueue no kernel (everything else takes the stream as its last argument)
 _NO_LAUNCH = {"pz_last_error", "pz_abi_version", "pz_gemm_kernel_name", "pz_norm_rows_per_part",
               "pz_decode_attn_ws_bytes", "pz_lora_wgrad_ws_bytes", "pz_debug_poison_lds",
-              "pz_image_resize_scratch_bytes", "pz_image_augment_scratch_bytes"}
+              "pz_image_resize_scratch_bytes", "pz_image_augment_scratch_bytes", "pz_expert_attn_bwd_ws_bytes"}
 # test instrument (tests/test_train_loop_gpu.py): with a word set, every launch is preceded on its stream by
 # pz_debug_poison_lds(word), so a kernel reading LDS it did not write sees NaN.  PZ_POISON_LDS=1 turns it on
 # for a whole process (0xffffffff).

@@ -184,13 +184,26 @@ class PiZeroDDP(torch.nn.Module):
         ar.ensure_grad()
         if broadcast and dist.is_initialized():
             dist.broadcast(ar.data, src=0, group=group)
-        # LoRA fine-tuning: the adapter region is reduced once, by finish(); a region in which nothing trains (the
-        # frozen base VLM weights, 2.3 B zeros of gradient) is left out of the all-reduce
-        skip = ()
-        if getattr(module, "has_lora", False):
-            skip = tuple(r for r in ("action", "vlm") if r in ar.region_range and not any(
-                module._requires_grad(n) for n in ar.order if ar.slots[n].region == r))
-        self.reducer = GradReducer(ar, region_marks(module), bucket_bytes, group, skip_regions=skip)
+        # LoRA fine-tuning: the adapter region is reduced once, by finish().  A region in which nothing trains (the
+        # frozen base VLM weights of a LoRA model, the whole VLM under train_vlm: False -- 2.3 B zeros of gradient) is
+        # left out of the all-reduce; the set is taken again at every synchronised forward, since TrainAgent freezes
+        # the VLM after it built this wrapper.
+        self.reducer = GradReducer(ar, region_marks(module), bucket_bytes, group, skip_regions=self._frozen_regions())
+
+    def _frozen_regions(self):
+        """the "action" / "vlm" regions of the arena without a trainable parameter"""
+        m, ar = self.module, self.module._arena
+        live = {ar.slots[n].region for n in ar.order if m._requires_grad(n)}
+        return frozenset(r for r in ("action", "vlm") if r in ar.region_range and r not in live)
+
+    def sync_regions(self):
+        """Take the set of regions without a trainable parameter again (every synchronised forward does): a region
+        frozen or thawed since the last synchronised step leaves or joins the all-reduce.  Returns the skipped set."""
+        skip = self._frozen_regions()
+        if skip != self.reducer.skip:
+            self.reducer.skip = skip
+            self.reducer._reset()
+        return skip
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -205,6 +218,7 @@ class PiZeroDDP(torch.nn.Module):
         eng = self.module._engine()
         if self._sync and dist.is_initialized() and (dist.get_world_size(self.reducer.group) > 1 or self.force_reduce):
             self.reducer.enabled = True
+            self.sync_regions()
             eng.hook = self.reducer.notify
             eng.post_backward = self.reducer.finish
         else:

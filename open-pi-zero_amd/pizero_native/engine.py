@@ -367,6 +367,10 @@ class Engine:
         # expert GEMMs then share the CUs with the vlm GeGLU GEMM (the dominant kernel: live roofline 2.32 vs
         # 2.19 ms per launch), so off
         self.expert_stream_fwd = False
+        # a model whose VLM has nothing trainable (train_vlm: False) under the block mask: the VLM runs forward-only
+        # into the joint K/V buffers and only the expert groups keep activations and run a backward.
+        # False: the full joint pass, whose VLM backward then feeds nothing.
+        self.vlm_forward_only = True
         # row pitch of SigLIP's MLP activations (fc1 output / pre-activation / their gradient, 4304 wide): rounded up
         # to 64 elements, so every row starts on a 128-B line (8704 B instead of 8608 B).  The GEMMs that stream
         # these rows run 2-8 % faster with bitwise-equal results (profiles/r04/ld_pad_ab.txt); the pad columns are
@@ -1066,11 +1070,13 @@ class Engine:
         self._jkv_holder = weakref.ref(tok)
         return kv
 
-    def _pre_attn_train(self, g, l, X, pos, st, Qj, Kj, Vj, dev, ada=None):
+    def _pre_attn_train(self, g, l, X, pos, st, Qj, Kj, Vj, dev, ada=None, Lq=None, qoff=None):
         """One group's input RMSNorm + q|k|v projection + RoPE + joint Q / K / V scatter of joint layer l
-        (paligemma/modules.py:7-21, mixture.py:162-215, joint_model.py:170-257)."""
+        (paligemma/modules.py:7-21, mixture.py:162-215, joint_model.py:170-257).  Lq / qoff: Qj holds Lq query tokens
+        per sample and the group's start at qoff (default: all L joint tokens, the group at g.off)."""
         d = self.d
-        L, Lp, nh, hd = d.L, d.Lp, d.nh, d.hd
+        L, Lp, nh, hd = d.L if Lq is None else Lq, d.Lp, d.nh, d.hd
+        qoff = g.off if qoff is None else qoff
         B = Qj.shape[0]
         p = f"{g.prefix}{l}."
         x = X[g.name]
@@ -1084,10 +1090,10 @@ class Engine:
             # Q / K / V (N1: no [M, 2560] qkv tensor, no split launch); rows too few for the 8-phase
             # kernel (the action expert's 320) take GEMM + qkv_rope_split (same bits)
             if not (self.fuse_qkv_rope and ops.gemm_qkv_rope(h, W, pos[g.name], self.rope(g.theta), Qj, Kj, Vj, g.T,
-                                                             nh, hd, L, g.off, Lp, g.off, lora=lora)):
+                                                             nh, hd, L, qoff, Lp, g.off, lora=lora)):
                 qkv = torch.empty(M, (nh + 2) * hd, device=dev, dtype=BF16)
                 ops.linear(h, W, qkv, lora=lora)
-                ops.qkv_rope_split(qkv, pos[g.name], self.rope(g.theta), Qj, Kj, Vj, B, g.T, nh, 1, hd, L, g.off, Lp,
+                ops.qkv_rope_split(qkv, pos[g.name], self.rope(g.theta), Qj, Kj, Vj, B, g.T, nh, 1, hd, L, qoff, Lp,
                                    g.off)
 
         u = self._linear(h, [p + f"self_attn.{k}_proj.weight" for k in "qkv"], self.qkv_w(p), None, True, gemm=proj)
@@ -1263,15 +1269,17 @@ class Engine:
         dO[g.name] = o
         dXm[g.name] = dxm
 
-    def _qkv_backward(self, g, gs, p, dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta, nh, hd, dev, A=None, l=None):
+    def _qkv_backward(self, g, gs, p, dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta, nh, hd, dev, A=None, l=None, qoff=None):
         """One group's q|k|v projection + input RMSNorm backward of a joint layer (mixture.py:162-215,
-        joint_model.py:170-257 + inverse RoPE): dQ / dK / dV rows of the group -> dX[g]."""
+        joint_model.py:170-257 + inverse RoPE): dQ / dK / dV rows of the group -> dX[g].  dQ holds L query tokens per
+        sample, the group's from qoff (default g.off)."""
+        qoff = g.off if qoff is None else qoff
         x = gs["x"]
         M = x.shape[0]
         W = (nh + 2) * hd
         dqkv = torch.empty(M, W, device=dev, dtype=BF16)
         ops.qkv_rope_split_bwd(None if gs.get("skip") else dQ, dK, dV, pos[g.name], self.rope(g.theta), dqkv,
-                               B, g.T, nh, 1, hd, L, g.off, Lp, g.off)
+                               B, g.T, nh, 1, hd, L, qoff, Lp, g.off)
         names = [p + f"self_attn.{k}_proj.weight" for k in "qkv"]
         rgs = [self.rg(n) for n in names]
         dh = torch.empty(M, g.hid, device=dev, dtype=BF16)
@@ -1422,6 +1430,134 @@ class Engine:
         sv.pop("_jkv_token", None)  # the joint K/V buffers are free for the next forward
         return dX
 
+    # ================================== frozen VLM: expert-only joint layers ==
+    @contextlib.contextmanager
+    def _bf16_weights(self):
+        """the inference routes on bf16 weights only (the forward-only VLM pass of training never reads fp8 codes)"""
+        f8, self.f8 = self.f8, None
+        try:
+            yield
+        finally:
+            self.f8 = f8
+
+    def _expert_kernels_ok(self, T):
+        """pz_expert_attn_fwd / _bwd take head_dim 256 and up to 1024 query rows per sample; other shapes run the GEMM
+        attention path on the expert's query rows"""
+        return self.d.hd == 256 and T * self.d.nh <= 1024
+
+    def _expert_layers_train(self, groups, X, pos, cnt, B, save, Kall, Vall):
+        """The expert groups' joint layers against the K/V rows [0, P) that the forward-only VLM pass left in
+        Kall / Vall [nL, B, Lp, hd]: their q|k|v epilogue scatters their K/V into rows [P, P + T), their T * nh query
+        rows per sample attend to all L keys (pz_expert_attn_fwd: O + log-sum-exp; outside its limits the GEMM path
+        with its P / tanh exports on those rows), their activations are saved as in _joint_layers_train."""
+        d = self.d
+        dev = X[groups[0].name].device
+        L, Lp, nh, hd, P = d.L, d.Lp, d.nh, d.hd, d.P
+        T = sum(g.T for g in groups)
+        W = nh * hd
+        kern = self._expert_kernels_ok(T)
+        ada = save.get("ada")
+        S = None
+        layers = []
+        for l in range(d.nL):
+            last = l == d.nL - 1
+            Qe = torch.empty(B, T, W, device=dev, dtype=BF16)
+            Kj, Vj = Kall[l], Vall[l]
+            st = {"Q": Qe, "K": Kj, "V": Vj, "g": {}}
+            for g in groups:
+                self._pre_attn_train(g, l, X, pos, st, Qe, Kj, Vj, dev, ada, Lq=T, qoff=g.off - P)
+            if kern:
+                Oall = torch.empty(B * T, W, device=dev, dtype=BF16)
+                lse = torch.empty(B, T * nh, device=dev, dtype=F32)
+                ops.expert_attn_fwd(Qe, T, 0, Kj, Vj, Oall, lse, B, nh, T, L, 1.0 / math.sqrt(hd), 50.0, cnt, P, d.C, P)
+                st["lse"], st["Oall"] = lse, Oall
+                if len(groups) == 1:
+                    Os = {groups[0].name: Oall}
+                else:  # untied proprio / action: each mixture's o_proj reads its own rows
+                    Os = {g.name: torch.empty(B * g.T, W, device=dev, dtype=BF16) for g in groups}
+                    for g in groups:
+                        ops.copy_rows(Oall[g.off - P:], W, T * W, Os[g.name], W, g.T * W, B, g.T, W)
+            else:
+                if S is None:
+                    S = torch.empty(B, T * nh, Lp, device=dev, dtype=F32)
+                Os = {g.name: torch.empty(B * g.T, W, device=dev, dtype=BF16) for g in groups}
+                live = [g for g in groups if not (last and g.skip_last)]
+                st["P"], st["tc"] = self._attn_gemm(Qe, Kj, Vj, S, Os, live, P, T, L, "full", cnt, B, export=True)
+            for g in groups:
+                gs = st["g"][g.name]
+                if last and g.skip_last:
+                    X[g.name] = None
+                    gs["skip"] = True
+                    continue
+                X[g.name] = self._post_attn(g, l, X[g.name], Os[g.name], ada.get(g.name) if ada else None, gs)
+            layers.append(st)
+            self._chk(f"expert fwd layer {l} (frozen VLM)", Q=Qe, O=Os, lse=st.get("lse"), P=st.get("P"), X=X)
+        save["joint"] = layers
+        return X
+
+    def _expert_layers_backward(self, groups, dX, pos, cnt, B, sv, beta):
+        """Backward of _expert_layers_train: per layer the expert groups' MLP / o_proj backward, the attention backward
+        for their query rows (pz_expert_attn_bwd: dQ and the dK / dV of key rows [P, P + T) only; outside its limits
+        the backward GEMMs on those rows), and their q|k|v backward.  Nothing is computed for the VLM rows."""
+        d = self.d
+        L, Lp, nh, hd, P = d.L, d.Lp, d.nh, d.hd, d.P
+        dev = next(v for v in dX.values() if v is not None).device
+        T = sum(g.T for g in groups)
+        W = nh * hd
+        ada = sv.get("ada") or {}
+        scale = 1.0 / math.sqrt(hd)
+        dP = dS = None
+        for l in reversed(range(d.nL)):
+            st = sv["joint"][l]
+            dQ = torch.empty(B, T, W, device=dev, dtype=BF16)
+            dK = torch.empty(B, Lp, hd, device=dev, dtype=BF16)
+            dV = torch.empty(B, Lp, hd, device=dev, dtype=BF16)
+            dO, dXm = {}, {}
+            for g in groups:
+                gs = st["g"][g.name]
+                if not gs.get("skip"):
+                    self._mlp_oproj_backward(g, gs, f"{g.prefix}{l}.", dX, dO, dXm, beta, nh, hd, dev, ada.get(g.name), l)
+            Qe, Kj, Vj = st["Q"], st["K"], st["V"]
+            if "lse" in st:
+                if len(groups) == 1:
+                    dOall = dO[groups[0].name]
+                else:  # a skipped mixture's output reaches nothing: dO = 0
+                    dOall = torch.zeros(B * T, W, device=dev, dtype=BF16)
+                    for g in groups:
+                        if g.name in dO:
+                            ops.copy_rows(dO[g.name], W, g.T * W, dOall[g.off - P:], W, T * W, B, g.T, W)
+                ops.expert_attn_bwd(Qe, T, 0, Kj, Vj, st["Oall"], st["lse"], dOall, dQ, dK[:, P:], dV[:, P:], P, T, B, nh,
+                                    T, L, scale, 50.0, cnt, P, d.C, P)
+            else:
+                Pm, tc = st["P"], st["tc"]
+                if dP is None:
+                    dP = torch.empty(B, T * nh, Lp, device=dev, dtype=F32)
+                    dS = torch.empty(B, T * nh, Lp, device=dev, dtype=BF16)
+                if len(dO) < len(groups):
+                    dP.zero_()
+                for g in groups:
+                    if g.name in dO:
+                        ops.gemm(g.T * nh, L, hd, dO[g.name], hd, True, Vj, hd, True, dP[:, (g.off - P) * nh:], Lp,
+                                 batch=B, sA=(g.T * nh * hd, 0), sB=(Lp * hd, 0), sC=(T * nh * Lp, 0))
+                ops.attn_softmax_bwd(Pm, dP, Lp, tc, dS, Lp, B * T * nh, L, scale, 50.0)
+                ops.gemm(T * nh, hd, Lp, dS, Lp, True, Kj, hd, False, dQ, hd, batch=B, sA=(T * nh * Lp, 0),
+                         sB=(Lp * hd, 0), sC=(T * nh * hd, 0))
+                ops.gemm(Lp, hd, T * nh, dS, Lp, False, Qe, hd, False, dK, hd, batch=B, sA=(T * nh * Lp, 0),
+                         sB=(T * nh * hd, 0), sC=(Lp * hd, 0))
+                first = True
+                for g in groups:
+                    if g.name in dO:
+                        ops.gemm(Lp, hd, g.T * nh, Pm[:, (g.off - P) * nh:], Lp, False, dO[g.name], hd, False, dV, hd,
+                                 batch=B, sA=(T * nh * Lp, 0), sB=(g.T * nh * hd, 0), sC=(Lp * hd, 0), beta=not first)
+                        first = False
+            for g in groups:
+                self._qkv_backward(g, st["g"][g.name], f"{g.prefix}{l}.", dQ, dK, dV, dX, dXm, pos, B, T, Lp, beta, nh,
+                                   hd, dev, ada.get(g.name), l, qoff=g.off - P)
+            self._chk(f"expert bwd layer {l} (frozen VLM)", dO=dO, dQ=dQ, dK=dK[:, P:P + T], dV=dV[:, P:P + T], dX=dX)
+            self._notify("joint", l)
+        sv.pop("_jkv_token", None)  # the joint K/V buffers are free for the next forward
+        return dX
+
     # ============================================================ training ==
     def _expert_rows(self, Xp, e3, B, sp):
         """{group: input rows} of the expert groups from the proprio rows Xp [B*C, aH] times sp and the action rows e3
@@ -1458,24 +1594,38 @@ class Engine:
     def train_forward(self, ids, pix, cnt, pos, proprios, actions, t, x0, save, prefix_len=None):
         """pizero.py:607-661: returns fp32 loss [1]; ``save`` collects activations.  ``prefix_len`` (int32 [B] on the
         device): rows h < prefix_len[b] are fed clean (psi = bf16(x1), time 1) and carry no loss; None
-        launches exactly the kernels of a run without the option."""
+        launches exactly the kernels of a run without the option.
+
+        With nothing trainable in the VLM (train_vlm: False; PiZero._vlm_needs_grad() false) and the block mask, the
+        frozen-VLM pass runs (``vlm_forward_only``): SigLIP, the projector and the vlm mixture forward-only
+        on the bf16 inference routes into the joint K/V buffers (no VLM activation and no SigLIP state is saved), then
+        the expert groups alone with their activations saved.  A GeneralMask keeps the full joint pass."""
         d = self.d
         if d.ada and prefix_len is not None:
             raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
         dev = pix.device
         B = ids.shape[0]
         tied = self.m._tied
-        sv_v = {}
-        img = self.siglip_forward(pix, sv_v)
-        Xv = self.embed_prefix(ids, img)
+        frozen = self.vlm_forward_only and not isinstance(cnt, GeneralMask) and not self.m._vlm_needs_grad()
+        if frozen:
+            sv_v = Xv = None
+            Kall, Vall = self._joint_kv(B, d.Lp, dev, save)
+            with self._bf16_weights():
+                self.prefill(ids, pix, cnt, pos["vlm"], None, None, Kall, Vall, with_proprio=False)
+        else:
+            sv_v = {}
+            img = self.siglip_forward(pix, sv_v)
+            Xv = self.embed_prefix(ids, img)
         prop = proprios.reshape(B * d.C, d.Pd).to(BF16)
         pe = torch.empty(B * d.C, d.aH, device=dev, dtype=BF16)
         ops.small_linear(prop, self.w("proprio_encoder.weight"), pe, bias=self.w("proprio_encoder.bias"))
         psi = torch.empty(B * d.H, d.A, device=dev, dtype=BF16)
         ops.flow_psi(x0, actions, t, psi, d.sig_min, prefix_len=prefix_len)
         e3 = self.action_embed(psi, t, save, prefix_len)
-        X = {"vlm": Xv, **self._expert_rows(pe, e3, B, math.sqrt(d.aH))}
-        groups = self.groups(tied)
+        X = self._expert_rows(pe, e3, B, math.sqrt(d.aH))
+        if not frozen:
+            X = {"vlm": Xv, **X}
+        groups = self.groups(tied, active=("proprio", "action")) if frozen else self.groups(tied)
         if d.ada:
             # the time condition (pizero.py:634; no parameters, t is data: no gradient flows into it) and every
             # adaLN site's modulation rows of the step, one GEMM per expert group
@@ -1483,7 +1633,10 @@ class Engine:
             ops.time_embed(t, cond, d.tmax, ref_bf16=d.time_bf16)
             save["cond"] = cond
             save["ada"] = {g.name: Ada(self, g, cond) for g in groups if g.name != "vlm"}
-        X = self._joint_layers_train(groups, X, pos, cnt, B, save)
+        if frozen:
+            X = self._expert_layers_train(groups, X, pos, cnt, B, save, Kall, Vall)
+        else:
+            X = self._joint_layers_train(groups, X, pos, cnt, B, save)
         ag, Tg = groups[-1].name, groups[-1].T
         aoff = d.C if tied else 0
         Xl = X[ag]
@@ -1496,7 +1649,8 @@ class Engine:
         ops.flow_loss(v[aoff:], 8, Tg * 8, x0, actions, loss, None, None, B, d.H, d.A, d.sig_min,
                       prefix_len=prefix_len)
         save.update(sv_v=sv_v, ids=ids, cnt=cnt, pos=pos, B=B, prop=prop, pe=pe, Xl=Xl, ya=ya, ra=ra,
-                    x0=x0, x1=actions, v=v, ag=ag, aoff=aoff, Tg=Tg, groups=groups, prefix_len=prefix_len)
+                    x0=x0, x1=actions, v=v, ag=ag, aoff=aoff, Tg=Tg, groups=groups, prefix_len=prefix_len,
+                    frozen=frozen)
         self._chk("train fwd head (action norm, decoder, flow loss)", embed=Xv, ya=ya, v=v, loss=loss)
         return loss
 
@@ -1528,7 +1682,10 @@ class Engine:
         self._chk("train bwd head", dv=dv, dya=dya, dXl=dXl)
         dX = {g.name: None for g in groups}
         dX[sv["ag"]] = dXl
-        dX = self._joint_layers_backward(groups, dX, sv["pos"], sv["cnt"], B, sv, beta)
+        if sv.get("frozen"):
+            dX = self._expert_layers_backward(groups, dX, sv["pos"], sv["cnt"], B, sv, beta)
+        else:
+            dX = self._joint_layers_backward(groups, dX, sv["pos"], sv["cnt"], B, sv, beta)
         if ada:
             # the expert's layer-0 backward is complete: every conditioning Linear's gradient (the arena block that
             # follows the expert layers) before the encoders' notification
@@ -1570,7 +1727,7 @@ class Engine:
             ops.colsum(de1, self.gw(ae + "linear_1.bias"), ws, beta=beta)
         self._notify("encoders", -1)
         # VLM prefix -> projector -> SigLIP
-        if self.m._vlm_needs_grad():
+        if not sv.get("frozen") and self.m._vlm_needs_grad():
             dimg = torch.empty(B * d.n_img, d.gH, device=dev, dtype=BF16)
             ops.embed_merge_bwd(sv["ids"], dX["vlm"], dimg, d.n_img, d.image_token, 1.0)
             self._chk("train bwd embed-merge", dimg=dimg)

@@ -27,6 +27,7 @@ from ._lib import (
     AdamW8Args,
     QkvRopeArgs,
     DecodeAttnArgs,
+    ExpertAttnBwdArgs,
     FlashArgs,
     GemmArgs,
     SmallGemmArgs,
@@ -502,8 +503,9 @@ def gemm_qkv_rope(x, W, pos, cs, q_out, k_out, v_out, T, nh, hd, Lq, qoff, Lk, k
     return True
 
 
-def decode_attn(q, Lq, qoff, k, v, o, B, nh, T, nk, scale, cap, cnt, prefix, cond, qtok0):
-    """Few-query joint attention (denoise): q [B, Lq, nh*hd] rows qoff.., k/v [B, Lk, hd], o [B*T, nh*hd]."""
+def decode_attn(q, Lq, qoff, k, v, o, B, nh, T, nk, scale, cap, cnt, prefix, cond, qtok0, lse=None):
+    """Few-query joint attention (denoise): q [B, Lq, nh*hd] rows qoff.., k/v [B, Lk, hd], o [B*T, nh*hd].
+    lse (fp32 [B, T*nh], expert_attn_fwd): the same launches also write each query row's log-sum-exp."""
     a = DecodeAttnArgs()
     a.q, a.ldq, a.Lq, a.qoff = _p(q), q.shape[-1], Lq, qoff
     a.k, a.v = _p(k), _p(v)
@@ -514,10 +516,47 @@ def decode_attn(q, Lq, qoff, k, v, o, B, nh, T, nk, scale, cap, cnt, prefix, con
     a.cnt, a.prefix, a.cond, a.qtok0 = _p(cnt), prefix, cond, qtok0
     need = lib().pz_decode_attn_ws_bytes(B, T * nh, nk)
     ws = workspace(o.device)  # the GEMM split-K scratch: stream-ordered, not in use between kernels
+    if ws.numel() * 4 < need and lse is not None:  # training micro-batches beyond the scratch (512 x bridge: 307 MB)
+        ws = torch.empty(need // 4, device=o.device, dtype=torch.float32)
     if ws.numel() * 4 < need:
         raise ValueError(f"decode_attn: {B} samples x {nk} keys need {need} B of workspace (> {ws.numel() * 4})")
     a.ws, a.ws_bytes = _p(ws), ws.numel() * 4
-    call("pz_decode_attn", C.byref(a), _st())
+    if lse is not None:
+        call("pz_expert_attn_fwd", C.byref(a), _p(lse), _st())
+    else:
+        call("pz_decode_attn", C.byref(a), _st())
+
+
+def expert_attn_fwd(q, Lq, qoff, k, v, o, lse, B, nh, T, nk, scale, cap, cnt, prefix, cond, qtok0):
+    """pz_expert_attn_fwd: decode_attn (the same O bits) + the fp32 log-sum-exp lse [B, T*nh] of every query row --
+    the forward of the action expert's training attention against a forward-only VLM."""
+    if lse is None:
+        raise ValueError("expert_attn_fwd: lse is required")
+    decode_attn(q, Lq, qoff, k, v, o, B, nh, T, nk, scale, cap, cnt, prefix, cond, qtok0, lse=lse)
+
+
+def expert_attn_bwd(q, Lq, qoff, k, v, o, lse, dO, dq, dk, dv, key0, nkeys, B, nh, T, nk, scale, cap, cnt, prefix, cond,
+                    qtok0, ws=None):
+    """pz_expert_attn_bwd: dq (addressed like q) and dk / dv [B, >= nkeys, hd] -- the rows of keys
+    [key0, key0 + nkeys), e.g. views dK[:, key0:] of [B, Lp, hd] buffers, whose other rows stay untouched -- from the
+    forward's q / k / v / o / lse and dO [B*T, nh*hd].  ws: fp32 scratch (default: allocated here)."""
+    a = ExpertAttnBwdArgs()
+    a.q, a.ldq, a.Lq, a.qoff = _p(q), q.shape[-1], Lq, qoff
+    a.k, a.v = _p(k), _p(v)
+    a.k_bstride, a.v_bstride = k.stride(0), v.stride(0)
+    a.o, a.ldo = _p(o), o.stride(0)
+    a.dO, a.lddo = _p(dO), dO.stride(0)
+    a.lse = _p(lse)
+    a.B, a.nh, a.T, a.nk, a.head_dim = B, nh, T, nk, k.shape[-1]
+    a.scale, a.cap = float(scale), float(cap)
+    a.cnt, a.prefix, a.cond, a.qtok0 = _p(cnt), prefix, cond, qtok0
+    a.dq, a.dk, a.dv = _p(dq), _p(dk), _p(dv)
+    a.dk_bstride, a.dv_bstride, a.key0, a.nkeys = dk.stride(0), dv.stride(0), key0, nkeys
+    need = lib().pz_expert_attn_bwd_ws_bytes(B, T * nh, nk, nkeys)
+    if ws is None:
+        ws = torch.empty(max(need // 4, 4), device=q.device, dtype=torch.float32)
+    a.ws, a.ws_bytes = _p(ws), ws.numel() * 4
+    call("pz_expert_attn_bwd", C.byref(a), _st())
 
 
 def attn_softmax(S, lds, P, ldp, R, N, scale, cap=0.0, tcap=None, mask_mode=0, rows_per_batch=1, heads=1,

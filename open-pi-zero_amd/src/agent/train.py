@@ -179,6 +179,9 @@ class TrainAgent:
         else:
             for p in model.trainable_vlm_parameters:
                 p.requires_grad = False
+            if self.main_rank and not model._vlm_needs_grad():
+                log.info("train_vlm False: frozen-VLM pass active (VLM forward-only, expert-only backward%s)",
+                         "; the frozen VLM region is left out of the all-reduce" if self.multi_gpu else "")
         self.flow_sampling = cfg_get(cfg, "flow_sampling", "beta")
         self.flow_t_max = 1 - float(cfg_get(cfg, "flow_sig_min", 0.001))
         self.flow_beta_dist = torch.distributions.Beta(float(cfg_get(cfg, "flow_alpha", 1.5)),
