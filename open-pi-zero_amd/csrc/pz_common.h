@@ -109,7 +109,7 @@ __device__ __forceinline__ float silu_grad(float x) {
 
 // ---- few-row GEMV path (pz_gemv.hip), chosen by pz_gemm's planner ------------------
 bool pz_gemv_supported(const pz_gemm_args* a);
-int pz_gemv_launch(const pz_gemm_args* a, hipStream_t st);
+int pz_gemv_launch(const pz_gemm_args* a, int mr, hipStream_t st);  // mr: rows per workgroup, 4 (M <= 4) | 8
 
 // ---- host side error plumbing -------------------------------------------------
 void pz_set_error(const char* fmt, ...);

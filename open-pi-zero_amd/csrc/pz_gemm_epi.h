@@ -1,5 +1,6 @@
-// GEMM argument block and the shared epilogue helpers (pz_gemm.hip, pz_gemm_rows.hip).
-// GemmP is a plain struct with ONE definition (both translation units include this header);
+// GEMM argument block and the shared epilogue helpers (pz_gemm.hip, pz_gemm_rows.hip, pz_gemm_tall.hip; the plan
+// and the launcher declarations: pz_gemm_plan.h).
+// GemmP is a plain struct with ONE definition (every GEMM translation unit includes this header);
 // the device helpers live in an anonymous namespace (each TU inlines its own copies).
 #pragma once
 
@@ -340,13 +341,3 @@ __device__ __forceinline__ void store_geglu4(const GemmP& p, int64_t cofs, int64
   }
 }
 }  // namespace
-// row-slab GEMM launcher (pz_gemm_rows.hip): w waves, tnb 16-column blocks per 64-row tile
-int pz_rows_launch(const GemmP& p, int w, int tnb, bool geglu, int f8w, hipStream_t st);
-// skinny-64 GEMM launcher (pz_gemm_rows.hip): M <= 64 rows (16 < M bf16, any with fp8 weights: W8A16), w waves,
-// 16 columns per block, mb 16-row blocks
-int pz_sk64_launch(const GemmP& p, int w, int mb, bool f8w, int64_t tiles_n, hipStream_t st);
-// tall-tile GEMM launcher (pz_gemm_tall.hip): 64 * mi rows per tile, k-contiguous A and B, plain epilogues,
-// split-K over blockIdx.y when splits > 1
-int pz_tall_launch(const GemmP& p, int mi, int splits, hipStream_t st);
-// split-K second pass (pz_gemm.hip): C = epilogue(sum of the S fp32 partial slabs in p.ws)
-int pz_splitk_epi_launch(const GemmP& p, int S, hipStream_t st);

@@ -1,7 +1,7 @@
 // Few-row (skinny-64) and row-slab GEMM kernels (own translation unit: pz_gemm.hip takes minutes to compile).
 #include <atomic>
 
-#include "pz_gemm_epi.h"
+#include "pz_gemm_plan.h"
 
 namespace {
 
@@ -548,96 +548,63 @@ __global__ void __launch_bounds__(W * 64) gemm_skinny64_kernel(GemmP p) {
 
 }  // namespace
 
-template <int W, int TMB, int TNB, bool GEGLU, bool F8W = false>
-static int launch_rows_k(const GemmP& p, hipStream_t st) {
-  constexpr int smem = W * (GEGLU ? 2 : 1) * TMB * TNB * 1024;
-  auto kern = gemm_rows_kernel<W, TMB, TNB, GEGLU, F8W>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(W * 64), smem, st, p);
+template <auto KERN, int W, int SMEM>
+static int launch_rows(const GemmP& p, hipStream_t st) {
+  pz_dyn_smem<KERN>(SMEM);
+  hipLaunchKernelGGL(KERN, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(W * 64), SMEM, st, p);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
 }
 
-template <int W>
-static int launch_rows_w(const GemmP& p, int tnb, bool geglu, hipStream_t st) {
-  if (geglu) return tnb == 2 ? launch_rows_k<W, 4, 2, true>(p, st) : launch_rows_k<W, 4, 1, true>(p, st);
-  if (tnb == 4) return launch_rows_k<W, 4, 4, false>(p, st);
-  if (tnb == 2) return launch_rows_k<W, 4, 2, false>(p, st);
-  return launch_rows_k<W, 4, 1, false>(p, st);
+// 64-row tiles (TMB = 4) of 1 | 2 | 4 16-column blocks (GeGLU: gate and up blocks, 1 | 2); rows_f8: 1 = W8A16 (bf16
+// rows, e4m3 weights), 2 = W8A8 (both e4m3, per-row activation scales)
+int pz_rows_launch(const GemmP& p, const Plan& pl, hipStream_t st) {
+  return with_int<8, 4>(pl.rows_w, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    if (pl.rows_f8 == 2)
+      return with_int<4, 2, 1>(pl.rows_tnb, [&](auto tnb) {
+        constexpr int TNB = decltype(tnb)::value;
+        return launch_rows<gemm_rows_f8a_kernel<W, 4, TNB>, W, W * 4 * TNB * 1024>(p, st);
+      });
+    return with_bool(pl.rows_f8 == 1, [&](auto f8w) {
+      constexpr bool F8W = decltype(f8w)::value;
+      if (pl.geglu)
+        return with_int<2, 1>(pl.rows_tnb, [&](auto tnb) {
+          constexpr int TNB = decltype(tnb)::value;
+          return launch_rows<gemm_rows_kernel<W, 4, TNB, true, F8W>, W, W * 2 * 4 * TNB * 1024>(p, st);
+        });
+      return with_int<4, 2, 1>(pl.rows_tnb, [&](auto tnb) {
+        constexpr int TNB = decltype(tnb)::value;
+        return launch_rows<gemm_rows_kernel<W, 4, TNB, false, F8W>, W, W * 4 * TNB * 1024>(p, st);
+      });
+    });
+  });
 }
 
-template <int W>
-static int launch_rows_f8(const GemmP& p, int tnb, bool geglu, hipStream_t st) {
-  if (geglu) return tnb == 2 ? launch_rows_k<W, 4, 2, true, true>(p, st) : launch_rows_k<W, 4, 1, true, true>(p, st);
-  if (tnb == 4) return launch_rows_k<W, 4, 4, false, true>(p, st);
-  if (tnb == 2) return launch_rows_k<W, 4, 2, false, true>(p, st);
-  return launch_rows_k<W, 4, 1, false, true>(p, st);
-}
-
-template <int W, int TNB>
-static int launch_rows_f8a_k(const GemmP& p, hipStream_t st) {
-  constexpr int smem = W * 4 * TNB * 1024;
-  auto kern = gemm_rows_f8a_kernel<W, 4, TNB>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(W * 64), smem, st, p);
-  PZ_CHECK_LAUNCH();
-  return PZ_OK;
-}
-
-template <int W>
-static int launch_rows_f8a(const GemmP& p, int tnb, hipStream_t st) {
-  if (tnb == 4) return launch_rows_f8a_k<W, 4>(p, st);
-  if (tnb == 2) return launch_rows_f8a_k<W, 2>(p, st);
-  return launch_rows_f8a_k<W, 1>(p, st);
-}
-
-// f8w: 1 = W8A16 (bf16 rows, e4m3 weights), 2 = W8A8 (both e4m3, per-row activation scales)
-int pz_rows_launch(const GemmP& p, int w, int tnb, bool geglu, int f8w, hipStream_t st) {
-  if (f8w == 2) return w == 8 ? launch_rows_f8a<8>(p, tnb, st) : launch_rows_f8a<4>(p, tnb, st);
-  if (f8w) return w == 8 ? launch_rows_f8<8>(p, tnb, geglu, st) : launch_rows_f8<4>(p, tnb, geglu, st);
-  return w == 8 ? launch_rows_w<8>(p, tnb, geglu, st) : launch_rows_w<4>(p, tnb, geglu, st);
-}
-
-// M <= 64 rows (one 64-row chunk), 16 columns per block
+// M <= 64 rows (one 64-row chunk), 16 columns per block, K split over blockIdx.z
 template <int W, int MB, bool F8W>
-static int launch_sk64(const GemmP& p0, int64_t tiles_n, hipStream_t st) {
+static int launch_sk64(const GemmP& p0, const Plan& pl, hipStream_t st) {
   GemmP p = p0;
-  const int S = p.ksplit > 0 ? (int)((p.K / 64 + p.ksplit / 64 - 1) / (p.ksplit / 64)) : 1;
-  // in-launch combine (PZ_SK64_FUSED=0: the two-launch form, A/B; read per call): each launch gets its own range
-  // of arrival counters, dealt round-robin in 256-counter steps (256 launches in flight before a range is reused)
-  const char* e = getenv("PZ_SK64_FUSED");
-  const bool fits = p.sk_tk >= 0;  // (pz_gemm: the tile-private slabs fit the workspace, forward bf16 epilogue)
+  const int S = pl.splits > 1 ? pl.splits : 1;
+  // in-launch combine: each launch gets its own range of arrival counters, dealt round-robin in 256-counter steps
+  // (256 launches in flight before a range is reused)
   p.sk_tk = -1;
-  if (S > 1 && S <= 8 && tiles_n <= 256 && fits && !(e && e[0] == '0')) {
+  if (pl.sk_fused) {
     static std::atomic<unsigned> next{0};
     p.sk_tk = (int)((next.fetch_add(1) % (SK_CTRS / 256)) * 256);
   }
-  hipLaunchKernelGGL((gemm_skinny64_kernel<W, 16, MB, F8W>), dim3((unsigned)tiles_n, 1, S), dim3(W * 64), 0, st, p);
+  hipLaunchKernelGGL((gemm_skinny64_kernel<W, 16, MB, F8W>), dim3((unsigned)pl.tiles_n, 1, S), dim3(W * 64), 0, st, p);
   PZ_CHECK_LAUNCH();
-  if (S > 1 && p.sk_tk < 0) return pz_splitk_epi_launch(p, S, st);
+  if (S > 1 && !pl.sk_fused) return pz_splitk_epi_launch(p, S, st);
   return PZ_OK;
 }
 
-template <bool F8W>
-static int launch_sk64_any(const GemmP& p, int w, int mb, int64_t tn, hipStream_t st) {
-  if (w == 8) {
-    if (mb == 1) return launch_sk64<8, 1, F8W>(p, tn, st);
-    if (mb == 2) return launch_sk64<8, 2, F8W>(p, tn, st);
-    return launch_sk64<8, 4, F8W>(p, tn, st);
-  }
-  if (mb == 1) return launch_sk64<4, 1, F8W>(p, tn, st);
-  if (mb == 2) return launch_sk64<4, 2, F8W>(p, tn, st);
-  return launch_sk64<4, 4, F8W>(p, tn, st);
-}
-
-int pz_sk64_launch(const GemmP& p, int w, int mb, bool f8w, int64_t tiles_n, hipStream_t st) {
-  return f8w ? launch_sk64_any<true>(p, w, mb, tiles_n, st) : launch_sk64_any<false>(p, w, mb, tiles_n, st);
+int pz_sk64_launch(const GemmP& p, const Plan& pl, hipStream_t st) {
+  return with_bool(pl.fp8 == 2, [&](auto f8w) {
+    return with_int<8, 4>(pl.skinny_w, [&](auto w) {
+      return with_int<1, 2, 4>(pl.skinny_mb, [&](auto mb) {
+        return launch_sk64<decltype(w)::value, decltype(mb)::value, decltype(f8w)::value>(p, pl, st);
+      });
+    });
+  });
 }

@@ -19,7 +19,7 @@
 // [rows][BKT] with the 16-B chunks XOR-swizzled by row (conflict-free ds_read_b128); the swizzle is
 // applied to each lane's global source because an LDS-DMA write is lane-linear.  A K tail
 // (K % BKT != 0, K % 8 == 0) clamps its source chunks in bounds and zeroes the A fragments past K.
-#include "pz_gemm_epi.h"
+#include "pz_gemm_plan.h"
 
 namespace {
 
@@ -195,21 +195,19 @@ __global__ void __launch_bounds__(512, 1) gemm_tall_kernel(GemmP p) {
 template <int MI, int NI, int BKT, int NSTAGE>
 static int launch_tall_k(const GemmP& p, int splits, hipStream_t st) {
   using C = TallCfg<MI, NI, BKT, NSTAGE>;
-  auto kern = gemm_tall_kernel<MI, NI, BKT, NSTAGE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n), (unsigned)splits), dim3(512), C::SMEM, st, p);
+  pz_dyn_smem<gemm_tall_kernel<MI, NI, BKT, NSTAGE>>(C::SMEM);
+  hipLaunchKernelGGL((gemm_tall_kernel<MI, NI, BKT, NSTAGE>), dim3((unsigned)(p.tiles_m * p.tiles_n), (unsigned)splits),
+                     dim3(512), C::SMEM, st, p);
   PZ_CHECK_LAUNCH();
   if (splits > 1) return pz_splitk_epi_launch(p, splits, st);
   return PZ_OK;
 }
 
-// 64-column tiles, 64-deep K-tiles in a 3-slot ring.  mi = 4 (256-row tiles) or 5 (320-row tiles).
+// 64-column tiles, 64-deep K-tiles in a 3-slot ring.  tall_mi = 4 (256-row tiles) or 5 (320-row tiles).
 // (A GeGLU form and a k-strided-B (NN dgrad) form measured slower on every Pi0 shape, profiles/r04/tall_bench.log,
 // and are gone.)
-int pz_tall_launch(const GemmP& p, int mi, int splits, hipStream_t st) {
-  return mi == 4 ? launch_tall_k<4, 2, 64, 3>(p, splits, st) : launch_tall_k<5, 2, 64, 3>(p, splits, st);
+int pz_tall_launch(const GemmP& p, const Plan& pl, hipStream_t st) {
+  return with_int<4, 5>(pl.tall_mi, [&](auto mi) {
+    return launch_tall_k<decltype(mi)::value, 2, 64, 3>(p, pl.splits > 1 ? pl.splits : 1, st);
+  });
 }

@@ -275,7 +275,7 @@ int launch_gemv(const GemvP& p, hipStream_t st) {
 
 }  // namespace
 
-// shape/epilogue support of the GEMV path (the planner in pz_gemm.hip asks before choosing it)
+// shape/epilogue support of the GEMV path (the planner in pz_gemm_host.hip asks before choosing it)
 bool pz_gemv_supported(const pz_gemm_args* a) {
   if (a->M < 1 || a->M > 8 || a->batch != 1 || !a->a_kcontig || !a->b_kcontig || a->fp8_mode) return false;
   if (a->K % 512 != 0 || a->epilogue > PZ_EPI_SILU) return false;
@@ -285,7 +285,7 @@ bool pz_gemv_supported(const pz_gemm_args* a) {
   return getenv("PZ_GEMV") == nullptr || getenv("PZ_GEMV")[0] != '0';
 }
 
-int pz_gemv_launch(const pz_gemm_args* a, hipStream_t st) {
+int pz_gemv_launch(const pz_gemm_args* a, int mr, hipStream_t st) {
   GemvP p{};
   p.x = (const bf16_t*)a->A;
   p.ldx = a->lda;
@@ -309,7 +309,7 @@ int pz_gemv_launch(const pz_gemm_args* a, hipStream_t st) {
   p.nw = (const bf16_t*)a->norm_w;
   p.neps = a->norm_eps;
   // columns per group: >= 256 workgroups for the Pi0 widths (N = 1024: 4 -> 256; GeGLU I = 4096: 4 -> 512)
-  if (a->M <= 4) {
+  if (mr == 4) {
     if (geglu) return launch_gemv<4, 4, true>(p, st);
     if (p.N <= 1024) return launch_gemv<4, 4, false>(p, st);
     return launch_gemv<4, 8, false>(p, st);

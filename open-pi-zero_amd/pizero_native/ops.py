@@ -253,7 +253,7 @@ def linear_fp8(x, Wq, w_scale, out, *, bias=None, resid=None, epi=PZ_EPI_NONE, a
 
 
 def rows_w8a16_ok(M, K, ncols):
-    """e4m3 weights with bf16 rows above 64 rows: the row-slab kernel's shapes (pz_gemm.hip plan_rows: 64 < M <=
+    """e4m3 weights with bf16 rows above 64 rows: the row-slab kernel's shapes (pz_gemm_host.hip plan_rows: 64 < M <=
     1024, K % 64 == 0, K <= 2048, <= 4096 output columns; PZ_GEMM_ROWS=0: never, =1: any K / width, as the planner).
     tests/test_abi.py::test_gemm_routes_golden holds this to the planner."""
     import os

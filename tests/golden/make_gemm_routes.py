@@ -1,6 +1,11 @@
 """Pin the GEMM planner's routing table: tests/golden/gemm_routes.json.
 
-    env -i PATH=$PATH python tests/golden/make_gemm_routes.py      (no PZ_* variable set)
+    env -i PATH=$PATH python tests/golden/make_gemm_routes.py            (no PZ_* variable set)
+    env -i PATH=$PATH python tests/golden/make_gemm_routes.py --knobs    (gemm_routes_knobs.json)
+
+--knobs sweeps the same grid once per setting of KNOBS (the planner's A/B switches) and stores, per setting, only the
+routes that differ from gemm_routes.json.  Record either fixture from a build of the commit whose routes are to be
+kept, never from the change under test.
 
 pz_gemm_kernel_name is host-only logic, and without a device the planner assumes 256 compute units (the MI355X
 count), so the table is the one the GPU machine routes by.  The fixture stores the axes, the unique kernel-name
@@ -58,6 +63,16 @@ AXES = {
 }
 
 
+# the planner's A/B switches ("Environment variables"), each swept over the whole grid by --knobs
+KNOBS_OUT = os.path.join(HERE, "gemm_routes_knobs.json")
+KNOBS = [
+    {"PZ_GEMM_TAIL": "0"}, {"PZ_GEMM_ROWS": "0"}, {"PZ_GEMM_ROWS": "1"}, {"PZ_GEMM_TALL": "0"}, {"PZ_GEMM_TALL": "1"},
+    {"PZ_ROWS_FIRST": "1"}, {"PZ_GEMV": "0"}, {"PZ_SK64_FUSED": "0"}, {"PZ_GEMV": "0", "PZ_SKINNY_MINNC": "4"},
+    {"PZ_GEMV": "0", "PZ_SKINNY_MINNC": "8"}, {"PZ_ROWS_W": "4"}, {"PZ_ROWS_W": "8"}, {"PZ_ROWS_TNB": "1"},
+    {"PZ_ROWS_TNB": "2"}, {"PZ_ROWS_TNB": "4"},
+]
+
+
 def accepted(M, N, K, akc, bkc, epi, fp8, batch, c_fp32, K2):
     """pz_gemm's argument checks, as far as the swept arguments reach them"""
     if K % 8 != 0 and (akc or bkc):
@@ -112,11 +127,58 @@ def decode(fx):
     return out
 
 
+def knob_runs(default, got, index):
+    """the routes that differ from the default table, as runs [first query, name index, repeat, ...]"""
+    runs = []
+    for i, (d, g) in enumerate(zip(default, got)):
+        if g == d:
+            continue
+        if runs and runs[-3] + runs[-1] == i and runs[-2] == index[g]:
+            runs[-1] += 1
+        else:
+            runs += [i, index[g], 1]
+    return runs
+
+
+def apply_runs(default, names, runs):
+    """the routing table of one knob setting: the default one with the setting's runs written over it"""
+    out = list(default)
+    for i, ix, n in zip(runs[0::3], runs[1::3], runs[2::3]):
+        out[i:i + n] = [names[ix]] * n
+    return out
+
+
+def main_knobs():
+    """gemm_routes_knobs.json: the same grid under each A/B setting of KNOBS, stored against gemm_routes.json"""
+    default = decode(json.load(open(OUT)))
+    assert route_names() == default, "the default routes differ from gemm_routes.json"
+    tables = []
+    for env in KNOBS:
+        os.environ.update(env)
+        tables.append(route_names())
+        for k in env:
+            del os.environ[k]
+    names = sorted(set(n for t in tables for n in t))
+    index = {n: i for i, n in enumerate(names)}
+    settings = []
+    for env, t in zip(KNOBS, tables):
+        runs = knob_runs(default, t, index)
+        assert apply_runs(default, names, runs) == t
+        settings.append({"env": env, "changed": sum(runs[2::3]), "runs": runs})
+        print(f"{env}: {settings[-1]['changed']} of {len(t)} routes differ from the default")
+    with open(KNOBS_OUT, "w") as f:
+        json.dump({"queries": len(default), "names": names, "settings": settings}, f, separators=(",", ":"))
+        f.write("\n")
+    print(f"{len(KNOBS)} settings, {os.path.getsize(KNOBS_OUT)} bytes -> {KNOBS_OUT}")
+
+
 def main():
     knobs = sorted(k for k in os.environ if k.startswith("PZ_"))
     if knobs:
         sys.exit(f"unset {knobs} first: the fixture holds the default routes")
     sys.path[:0] = [ROOT, os.path.join(ROOT, "open-pi-zero_amd")]
+    if "--knobs" in sys.argv:
+        return main_knobs()
     got = route_names()
     names = sorted(set(got))
     index = {n: i for i, n in enumerate(names)}

@@ -48,7 +48,7 @@ def test_error_path_without_gpu():
 
 def test_gemm_planner_routes_without_gpu():
     """pz_gemm_kernel_name is host logic (no device needed): the row-slab kernel takes the measured-faster
-    64 < M <= 512 forward shapes (pz_gemm.hip plan_rows), the tile kernels keep the rest."""
+    64 < M <= 512 forward shapes (pz_gemm_host.hip plan_rows), the tile kernels keep the rest."""
     from pizero_native import ops
 
     geglu = ops.PZ_EPI_GEGLU
@@ -113,6 +113,36 @@ def test_gemm_routes_golden(monkeypatch):
                 mirror.append((M, N, K, kw, got))
     assert not bad, f"{len(bad)} of {len(qs)} routes changed, first: {bad[:5]}"
     assert not mirror, f"ops.rows_w8a16_ok disagrees with the planner on {len(mirror)} shapes, first: {mirror[:5]}"
+
+
+def test_gemm_routes_knobs_golden(monkeypatch):
+    """The routing table under each of the planner's A/B switches (tests/golden/gemm_routes_knobs.json, written by
+    make_gemm_routes.py --knobs from the library as it stood before the planner moved to pz_gemm_host.hip and every
+    switch read moved into make_plan): for each setting, every kernel name of the whole grid, stored as the routes
+    that differ from the default table."""
+    import json
+
+    from pizero_native import ops
+
+    for k in [k for k in os.environ if k.startswith("PZ_")]:
+        monkeypatch.delenv(k)
+    mk = _load_make_gemm_routes()
+    fx0 = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_routes.json")))
+    fx = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_routes_knobs.json")))
+    default = mk.decode(fx0)
+    qs = list(mk.queries(fx0["axes"]))
+    assert len(qs) == len(default) == fx["queries"]
+    assert [s["env"] for s in fx["settings"]] == mk.KNOBS
+    for s in fx["settings"]:
+        want = mk.apply_runs(default, fx["names"], s["runs"])
+        assert sum(w != d for w, d in zip(want, default)) == s["changed"] > 0
+        for k, v in s["env"].items():
+            monkeypatch.setenv(k, v)
+        bad = [(M, N, K, kw, got, w) for (M, N, K, kw), w in zip(qs, want)
+               if (got := ops.gemm_kernel_name(M, N, K, **kw)) != w]
+        for k in s["env"]:
+            monkeypatch.delenv(k)
+        assert not bad, f"{s['env']}: {len(bad)} of {len(qs)} routes changed, first: {bad[:5]}"
 
 
 def test_env_knob_census():
