@@ -672,6 +672,38 @@ int pz_episode_gather_rows(const void* action, const void* proprio, const void* 
                            void* out_action, void* out_proprio, void* out_pad_mask, void* out_input_ids,
                            void* out_attention_mask, void* stream);
 
+/* Input gradient of a Linear for a handful of rows (csrc/pz_dgrad_rows.hip).  Entry points added under ABI 22 (no
+ * existing signature changed).
+ *   dx[M, K] = epi(dy[M, N] @ W[N, K]): bf16 in and out, fp32 accumulation; W row-major [N, K] (row stride ldw) as the
+ *   arena holds it; dy, dx and aux row-strided.  M <= 16, N % 8 == 0, K % 8 == 0.  epilogue PZ_EPI_NONE, or
+ *   PZ_EPI_DGEGLU: aux = saved [g | u] [M, 2K], dx is [M, 2K] (as pz_gemm's epilogue; dx may be aux).
+ * The reduction runs along W's rows, split over workgroups into fp32 slabs in ws (pz_dgrad_rows_ws_bytes(M, N, K)
+ * bytes, 16-byte aligned, caller-owned); a second launch sums the slabs in fixed order and applies the epilogue.  No
+ * atomics: the result does not depend on what ws or dx held.
+ * PZ_ERR_UNSUPPORTED, nothing launched and dx untouched, for every shape, epilogue or layout outside those limits (W
+ * rows not 16-byte aligned, dx / aux rows not 8-byte aligned): the caller runs pz_gemm.  pz_dgrad_rows_ws_bytes
+ * returns 0 for such a shape.  PZ_ERR_INVALID_ARG for null pointers and a workspace that is too small. */
+int64_t pz_dgrad_rows_ws_bytes(int64_t M, int64_t N, int64_t K);
+int pz_dgrad_rows(const void* dy, int64_t lddy, const void* W, int64_t ldw, void* dx, int64_t lddx, int64_t M,
+                  int64_t N, int64_t K, int32_t epilogue, const void* aux, int64_t ld_aux, void* ws, int64_t ws_bytes,
+                  void* stream);
+
+/* Guidance arithmetic of inference-time real-time chunking (csrc/pz_rtc.hip).  Entry points added under
+ * ABI 22.  fp32 multiplies and adds in the order written, each rounded by itself (no FMA contraction):
+ *   pz_rtc_seed:  e[b, h, c] = w[b, h] * (target[b, h, c] - (action[b, h, c] + (1 - t[b]) * v[b, h, c]))
+ *                 action, target, e fp32 [B, H, A]; w fp32 [B, H]; t fp32 [B]; v bf16 addressed as pz_euler_step's
+ *                 (v[b * v_bstride + h * ldv + c]).  dv bf16 [B * T, 8]: row b * T + row0 + h, column c < A gets
+ *                 bf16(e[b, h, c]); every other element (pad columns, the rows outside [row0, row0 + H)) gets 0.
+ *   pz_rtc_euler: g = e + (1 - t[b]) * dA[b * H + h, c]  (dA bf16, row stride ldda)
+ *                 action = action + dt * (v + coef[k] * g);  then t[b] += dt, once per sample.
+ *                 coef fp32 [steps] on the device, 0 <= k < steps (checked on the host). */
+int pz_rtc_seed(const float* action, const void* v, int64_t ldv, int64_t v_bstride, const float* target,
+                const float* w, const float* t, float* e, void* dv, int64_t T, int64_t row0, int64_t B, int64_t H,
+                int64_t A, void* stream);
+int pz_rtc_euler(float* action, const void* v, int64_t ldv, int64_t v_bstride, const float* e, const void* dA,
+                 int64_t ldda, float* t, const float* coef, int64_t steps, int64_t k, int64_t B, int64_t H, int64_t A,
+                 float dt, void* stream);
+
 /* test instrument: fill every CU's LDS with `word` (0xffffffff = NaN) on `stream`, so the next kernel's reads of
  * LDS it did not write return NaN (tests/test_train_loop_gpu.py; _lib.call runs it before every launch under
  * PZ_POISON_LDS=1).  Not on any product path. */

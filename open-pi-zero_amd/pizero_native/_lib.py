@@ -229,6 +229,11 @@ SIGNATURES = {
     "pz_episode_gather_frames": [vp, i64, i64, i64, i64, vp, i64, vp, vp],
     "pz_episode_gather_rows": [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp,
                                vp],
+    # few-row input gradient (csrc/pz_dgrad_rows.hip) and the guidance arithmetic of DESIGN 7i (csrc/pz_rtc.hip)
+    "pz_dgrad_rows_ws_bytes": [i64, i64, i64],
+    "pz_dgrad_rows": [vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, vp, i64, vp, i64, vp],
+    "pz_rtc_seed": [vp, vp, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp],
+    "pz_rtc_euler": [vp, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, f32, vp],
     "pz_debug_poison_lds": [C.c_uint32, vp],
     "pz_debug_spin": [i64, i64, vp],
     "pz_last_error": [],
@@ -236,7 +241,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"pz_last_error": C.c_char_p, "pz_gemm_kernel_name": C.c_char_p, "pz_norm_rows_per_part": i64,
             "pz_decode_attn_ws_bytes": i64, "pz_lora_wgrad_ws_bytes": i64, "pz_image_resize_scratch_bytes": i64,
-            "pz_image_augment_scratch_bytes": i64, "pz_expert_attn_bwd_ws_bytes": i64}
+            "pz_image_augment_scratch_bytes": i64, "pz_expert_attn_bwd_ws_bytes": i64, "pz_dgrad_rows_ws_bytes": i64}
 
 _lib = None
 
@@ -267,7 +272,8 @@ def lib():
 # entry points that enqueue no kernel (everything else takes the stream as its last argument)
 _NO_LAUNCH = {"pz_last_error", "pz_abi_version", "pz_gemm_kernel_name", "pz_norm_rows_per_part",
               "pz_decode_attn_ws_bytes", "pz_lora_wgrad_ws_bytes", "pz_debug_poison_lds",
-              "pz_image_resize_scratch_bytes", "pz_image_augment_scratch_bytes", "pz_expert_attn_bwd_ws_bytes"}
+              "pz_image_resize_scratch_bytes", "pz_image_augment_scratch_bytes", "pz_expert_attn_bwd_ws_bytes",
+              "pz_dgrad_rows_ws_bytes"}
 # test instrument (tests/test_train_loop_gpu.py): with a word set, every launch is preceded on its stream by
 # pz_debug_poison_lds(word), so a kernel reading LDS it did not write sees NaN.  PZ_POISON_LDS=1 turns it on
 # for a whole process (0xffffffff).

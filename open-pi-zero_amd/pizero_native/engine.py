@@ -192,6 +192,18 @@ PREFIX_ADAPTIVE_MSG = ("an action prefix (action_prefix_max_delay / prefix_len, 
                        "and a prefix row needs its own (time 1)")
 
 
+# inference-time guidance toward the previous chunk: what it does not combine with, by config key
+GUIDE_ADAPTIVE_MSG = ("action guidance (action_guidance_beta / overlap, DESIGN 7i) is not available with "
+                      "action_expert_adaptive_mode (adaLN / adaLN-Zero): the guided step differentiates the plain "
+                      "expert's saved activations only")
+GUIDE_FP8_MSG = ("action guidance (action_guidance_beta / overlap, DESIGN 7i) is not available with fp8 inference "
+                 "(prepare_fp8 / infer_fp8): the vector-Jacobian product runs on the bf16 weights")
+GUIDE_MASK_MSG = ("action guidance (action_guidance_beta / overlap, DESIGN 7i) needs the Pi0 block mask: a GeneralMask "
+                  "is not supported")
+GUIDE_PREFIX_MSG = ("action guidance (overlap, DESIGN 7i) and a hard action prefix (prefix_len, DESIGN 7f) do not "
+                    "compose: guidance replaces the prefix inside the loop")
+
+
 class Ada:
     """Time modulation of one adaLN expert group for one forward / denoise step: ``mod`` fp32 [B, nslots * hidden],
     every site's gamma_pre / beta / gate_pre rows (cond @ W^T, biases added by the row kernels), from ONE GEMM of
@@ -392,6 +404,13 @@ class Engine:
         self._merged = None
         self._merged_ver = None
         self._infer = False
+        # the guided denoise step runs the training backward of the expert rows for the input gradient
+        # alone: while set, no weight gradient, column sum, norm-weight partial or hook notification is launched
+        # (rg() answers False, requires_grad is not touched) and no adapter site is used (the merged weights are read)
+        self._dgrad_only = False
+        # ... and its few-row input-gradient GEMMs take pz_dgrad_rows where it measured faster (_dgrad_gemm; False:
+        # always pz_gemm, the A/B arm)
+        self.dgrad_rows = True
         if self.d.nkv != 1:
             raise NotImplementedError("joint attention kernel path assumes MQA (num_key_value_heads=1, bridge.yaml:176)")
 
@@ -407,7 +426,7 @@ class Engine:
 
     def _chk(self, where, **tensors):
         """PZ_CHECK_FINITE: raise on the first non-finite tensor of this stage (no-op otherwise)"""
-        if not self.check_finite:
+        if not self.check_finite or torch.cuda.is_current_stream_capturing():
             return
         check_finite(where, **tensors)
 
@@ -425,7 +444,7 @@ class Engine:
     # --------------------------------------------------------------- LoRA --
     def lora(self, *wnames):
         """LoraSite of the Linear(s) ``wnames`` (fused along N, in column order) or None without adapters"""
-        if wnames[0] not in self._lora_w:
+        if wnames[0] not in self._lora_w or self._dgrad_only:
             return None
         st = self._lora_sites.get(wnames)
         if st is None:
@@ -459,7 +478,17 @@ class Engine:
             site.grads(x, u, dy, lo[0], beta)
         if wgrad is not None:
             wgrad()
-        ops.linear_dgrad(dy, W, dx, lora=lo, **kw)
+        self._dgrad_gemm(dy, W, dx, lora=lo, **kw)
+
+    def _dgrad_gemm(self, dy, W, dx, lora=None, **kw):
+        """ops.linear_dgrad; in the guided denoise step (a handful of rows) pz_dgrad_rows where it measured faster and
+        takes the call: W [N, K] with N < K (down_proj 1024 -> 4096: 12.3 vs 13.2 us, o_proj 1024 -> 2048: 11.3 vs
+        11.6 us at M = 5), not N > K (gate|up 8192 -> 1024: 18.2 vs 16.4 us, q|k|v 2560 -> 1024: 12.5 vs 11.5 us;
+        profiles/rtc/rtc_bench.txt); N = K was not measured and stays on pz_gemm"""
+        if self._dgrad_only and self.dgrad_rows and lora is None and set(kw) <= {"epi", "aux"} and \
+                W.shape[0] < W.shape[1] and ops.linear_dgrad_rows(dy, W, dx, **kw):
+            return
+        ops.linear_dgrad(dy, W, dx, lora=lora, **kw)
 
     def lora_refresh(self):
         """Merged inference weights W + s B A of every adapted Linear (the reference merges on eval(), lora.py:186-199)
@@ -490,7 +519,7 @@ class Engine:
         return self.ar.grad_view(name)
 
     def rg(self, name):
-        return self.m._requires_grad(name)
+        return not self._dgrad_only and self.m._requires_grad(name)
 
     def qkv_w(self, p):
         return self.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight")
@@ -912,8 +941,10 @@ class Engine:
         accumulates its modulation gradient rows instead, Ada.weight_grads)"""
         if A is not None:
             return A.norm_bwd(dh, x, rstd, l, site, g.T, dx, dres=dres)
-        rpp = ops.rows_per_part()
         name = self._rms_name(g, l, site)
+        if self._dgrad_only:
+            return ops.rmsnorm_bwd(dh, x, self.w(name + "weight"), rstd, dx, dres=dres)
+        rpp = ops.rows_per_part()
         part = torch.empty((x.shape[0] + rpp - 1) // rpp, g.hid, device=x.device, dtype=F32)
         ops.rmsnorm_bwd(dh, x, self.w(name + "weight"), rstd, dx, dres=dres, dw_part=part)
         self._norm_grads(name, part, None, beta)
@@ -2097,8 +2128,89 @@ class Engine:
         ops.euler_step(action, v[aoff:], 8, ga.T * 8, t, B, d.H, d.A, 1.0 / d.steps)
 
     @_merged_weights
+    def denoise_step_guided(self, action, t, Xp, pos, cnt, kcache, vcache, B, guide, k):
+        """Euler step k of the loop guided toward the previous chunk:
+
+            v = expert(A_t, t);  e = w (.) (target - (A_t + (1 - t) v));  g = e + (1 - t) (dv/dA_t)^T e
+            A_t += dt (v + coef[k] g);  t += dt
+
+        guide = (target fp32 [B, H, A], w fp32 [B, H], coef fp32 [steps]) on the device.  The expert rows of every
+        sample (its proprio rows again, then the action rows: the frozen-VLM training pass, _expert_layers_train) run
+        forward with saved activations against the cached vlm K/V, their own K/V scattered into the cache rows as
+        denoise_step does; pz_rtc_seed turns v into the backward seed; the training backward then runs down to the
+        action encoder's input with every weight-gradient launch switched off (_dgrad_only; the proprio rows' input
+        gradient is dropped), and pz_rtc_euler applies the update.  Xp: the proprio rows times sqrt(hidden)."""
+        d = self.d
+        dev = action.device
+        target, w, coef = guide
+        groups = self.groups(self.m._tied, active=("proprio", "action"))
+        ga = groups[-1]  # the group that holds the action rows: the tied group's follow its proprio rows
+        aoff = ga.T - d.H
+        R = B * ga.T
+        save = {}
+        psi = torch.empty(B * d.H, d.A, device=dev, dtype=BF16)
+        ops.cast_to_bf16(action, psi)
+        X = self._expert_rows(Xp, self.action_embed(psi, t, save), B, None)
+        prev, self._dgrad_only = self._dgrad_only, True
+        try:
+            X = self._expert_layers_train(groups, X, pos, cnt, B, save, kcache, vcache)
+            Xl = X[ga.name]
+            ya = torch.empty_like(Xl)
+            ra = torch.empty(R, device=dev, dtype=F32)
+            self._norm_fwd(None, ga, Xl, "norm", "", ya, ra)
+            v = torch.empty(R, 8, device=dev, dtype=BF16)
+            wd = self.w("action_decoder.weight")
+            ops.small_linear(ya, wd, v, bias=self.w("action_decoder.bias"))
+            e = torch.empty(B, d.H, d.A, device=dev, dtype=F32)
+            dv = torch.empty(R, 8, device=dev, dtype=BF16)
+            ops.rtc_seed(action, v[aoff:], 8, ga.T * 8, target, w, t, e, dv, ga.T, aoff)
+            # the backward of train_backward from dv down to de1, input gradients only
+            dya = torch.empty(R, d.aH, device=dev, dtype=BF16)
+            ops.small_gemm(R, d.aH, d.A, dv, 8, 1, wd, d.aH, 1, dya, d.aH)
+            dXl = torch.empty_like(dya)
+            self._norm_bwd(None, ga, dya, Xl, ra, "norm", "", dXl, None, False)
+            dX = {g.name: None for g in groups}
+            dX[ga.name] = dXl
+            dX = self._expert_layers_backward(groups, dX, pos, cnt, B, save, False)
+            dpe = torch.empty(B * d.C, d.aH, device=dev, dtype=BF16)
+            de3 = torch.empty(B * d.H, d.aH, device=dev, dtype=BF16)
+            self._expert_rows_bwd(dX, B, dpe, de3)
+            ae = "action_encoder."
+            de2 = torch.empty_like(de3)
+            self._dgrad_gemm(de3, self.w(ae + "linear_3.weight"), de2)
+            ops.act_bwd(de2, save["ae_pre"], de2, None, PZ_EPI_SILU)
+            dcat = torch.empty(B * d.H, 2 * d.aH, device=dev, dtype=BF16)
+            self._dgrad_gemm(de2, self.w(ae + "linear_2.weight"), dcat)
+            de1 = torch.empty_like(de3)
+            ops.split_time_grad(dcat, de1, B * d.H, d.aH)
+            dA = torch.empty(B * d.H, 8, device=dev, dtype=BF16)  # columns 0..A-1 written and read
+            ops.small_gemm(B * d.H, d.A, d.aH, de1, d.aH, 1, self.w(ae + "linear_1.weight"), d.A, 1, dA, 8)
+            ops.rtc_euler(action, v[aoff:], 8, ga.T * 8, e, dA[:, : d.A], t, coef, k, 1.0 / d.steps)
+        finally:
+            self._dgrad_only = prev
+        return dA
+
+    def _guide_args(self, guide, B, cnt, prefix_len):
+        """the refusals of the guided loop (by config key) and its device inputs"""
+        d = self.d
+        if d.ada:
+            raise NotImplementedError(GUIDE_ADAPTIVE_MSG)
+        if self.f8 is not None:
+            raise NotImplementedError(GUIDE_FP8_MSG)
+        if isinstance(cnt, GeneralMask):
+            raise NotImplementedError(GUIDE_MASK_MSG)
+        if prefix_len is not None:
+            raise NotImplementedError(GUIDE_PREFIX_MSG)
+        target, w, coef = guide
+        for name, x, shape in (("target", target, (B, d.H, d.A)), ("w", w, (B, d.H)), ("coef", coef, (d.steps,))):
+            if not (torch.is_tensor(x) and x.is_cuda and x.dtype == F32 and x.is_contiguous()
+                    and tuple(x.shape) == shape):
+                raise ValueError(f"infer_action: guide {name} must be a contiguous fp32 device tensor of shape {shape}")
+        return target, w, coef
+
+    @_merged_weights
     def infer_action(self, ids, pix, cnt, vpos, ppos, apos, proprios, noise, kcache, vcache, clip=True, prefix=None,
-                     prefix_len=None):
+                     prefix_len=None, guide=None):
         """pizero.py:416-490.  With an adaLN expert both this and PiZero.infer_action_naive compute the naive
         semantics (pizero.py:492-557): the reference's cached infer_action raises AttributeError there ('NoneType'
         object has no attribute 'ndim' -- its prefill runs the proprio mixture without the time condition), and
@@ -2107,12 +2219,19 @@ class Engine:
         ``prefix`` (fp32 [B, H, A], normalised action units) with ``prefix_len`` (int32 [B] on the device):
         rows h < prefix_len[b] of the chunk are the committed actions -- written over the noise before the first step
         (one launch more per chunk), embedded with time 1, never updated, exempt from the final clamp and returned
-        bit for bit; the other rows are denoised around them.  Neither given: exactly the launches of before."""
+        bit for bit; the other rows are denoised around them.  Neither given: exactly the launches of before.
+
+        ``guide`` = (target fp32 [B, H, A] in normalised action units, w fp32 [B, H], coef fp32 [steps]) on the device
+        (src/agent/chunking.py makes w and coef): every Euler step is steered toward ``target`` by the
+        vector-Jacobian product of the denoiser (denoise_step_guided).  No row is frozen, every row is embedded with
+        the sample's t, and the final clamp covers every row.  None: exactly the launches of before."""
         d = self.d
         B = ids.shape[0]
         dev = pix.device
         if (prefix is None) != (prefix_len is None):
             raise ValueError("infer_action: prefix and prefix_len go together")
+        if guide is not None:
+            guide = self._guide_args(guide, B, cnt, prefix_len)
         if prefix_len is not None and d.ada:
             raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
         self.fp8_refresh()
@@ -2129,6 +2248,20 @@ class Engine:
                 m[:, d.C:, :] = cnt.act
                 cnt = GeneralMask(itp=cnt.itp, act=m)
             step = functools.partial(self.denoise_step_ada, Xp=Xp, pos=pos)
+        elif guide is not None:
+            self.prefill(ids, pix, cnt, vpos, ppos, proprios, kcache, vcache)
+            if self.m._tied:
+                pos = {"expert": torch.cat([ppos, apos], dim=1).contiguous()}
+            else:
+                pos = {"proprio": ppos, "action": apos}
+            Xp = self._proprio_rows(proprios, B, dev)
+            action = noise.clone()
+            t = torch.zeros(B, device=dev, dtype=F32)
+            for k in range(d.steps):
+                self.denoise_step_guided(action, t, Xp, pos, cnt, kcache, vcache, B, guide, k)
+            if clip and d.clip is not None:
+                ops.clamp_(action, -d.clip, d.clip)
+            return action
         else:
             self.prefill(ids, pix, cnt, vpos, ppos, proprios, kcache, vcache)
             step = functools.partial(self.denoise_step, apos=apos)
@@ -2150,5 +2283,5 @@ class Engine:
 
     def _notify(self, stage, layer, streams=()):
         """streams: side streams (besides the current one) whose enqueued work produced some of those gradients"""
-        if self.hook is not None:
+        if self.hook is not None and not self._dgrad_only:
             self.hook(stage, layer, streams)

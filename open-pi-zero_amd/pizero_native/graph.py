@@ -43,11 +43,32 @@ def _load_prefix(static, name, prefix, prefix_len, H, **kw):
     static[name].copy_(torch.as_tensor(prefix).reshape(static[name].shape), **kw)
 
 
+def _load_guide(static, target, w, coef, **kw):
+    """copy the guidance inputs of a guidance-capable graph; none given: weights 0, the unguided chunk"""
+    if "guide_w" not in static:
+        if target is not None or w is not None or coef is not None:
+            raise ValueError("this graph takes no action guidance: call enable_guidance() before capture()")
+        return
+    if target is None and w is None and coef is None:
+        static["guide_w"].zero_()
+        return
+    if target is None or w is None or coef is None:
+        raise ValueError("the guidance target, its row weights and the coefficient table go together")
+    for name, x in (("guide_target", target), ("guide_w", w), ("guide_coef", coef)):
+        x = torch.as_tensor(x)
+        if x.numel() != static[name].numel():
+            raise ValueError(f"{name} must have shape {tuple(static[name].shape)}, got {tuple(x.shape)}")
+        static[name].copy_(x.reshape(static[name].shape), **kw)
+
+
 class InferenceGraph:
     """After ``enable_prefix()`` the graph also takes a committed action prefix (normalised units) and its
-    per-sample length as static inputs; without that call it is the graph it always was."""
+    per-sample length as static inputs; without that call it is the graph it always was.
+    After ``enable_guidance()`` it runs the guided loop on the static inputs ``guide_target`` (normalised
+    units), ``guide_w`` and ``guide_coef``; a graph takes one of the two options, not both."""
 
     prefix = False
+    guidance = False
     PREFIX_INPUT = "prefix"
 
     def __init__(self, model, bsz, clip=True):
@@ -79,6 +100,10 @@ class InferenceGraph:
             from .engine import PREFIX_ADAPTIVE_MSG
 
             raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
+        if self.guidance:
+            from .engine import GUIDE_PREFIX_MSG
+
+            raise NotImplementedError(GUIDE_PREFIX_MSG)
         if not self.prefix:
             if self.graph is not None:
                 raise RuntimeError("enable_prefix() must precede capture()")
@@ -86,15 +111,52 @@ class InferenceGraph:
             self.prefix = True
         return self
 
+    def enable_guidance(self):
+        """add the guidance target, its row weights and the per-step coefficients to the static inputs (before
+        capture()): the captured loop is the guided one, and one capture serves every target, delay, overlap and
+        beta.  Weights of 0, the state after this call, give the unguided chunk (through the guided step's kernels,
+        so within rounding, not bit for bit).  Returns self."""
+        e = self.m._engine()
+        from .engine import GUIDE_ADAPTIVE_MSG, GUIDE_FP8_MSG, GUIDE_PREFIX_MSG
+
+        if e.d.ada:
+            raise NotImplementedError(GUIDE_ADAPTIVE_MSG)
+        if e.f8 is not None:
+            raise NotImplementedError(GUIDE_FP8_MSG)
+        if self.prefix:
+            raise NotImplementedError(GUIDE_PREFIX_MSG)
+        if not self.guidance:
+            if self.graph is not None:
+                raise RuntimeError("enable_guidance() must precede capture()")
+            self._guide_static()
+            self.guidance = True
+        return self
+
+    def _guide_static(self):
+        s, d = self.static, self.m._engine().d
+        s["guide_target"] = torch.zeros_like(s["noise"])
+        s["guide_w"] = torch.zeros(s["noise"].shape[:2], device=s["noise"].device, dtype=torch.float32)
+        s["guide_coef"] = torch.zeros(d.steps, device=s["noise"].device, dtype=torch.float32)
+
+    def _guide(self, target=None):
+        """the engine's guide argument from the static inputs (None without the option)"""
+        s = self.static
+        if not self.guidance:
+            return None
+        return (s["guide_target"] if target is None else target, s["guide_w"], s["guide_coef"])
+
     def _run(self):
         s = self.static
         return self.m._engine().infer_action(s["ids"], s["pix"], s["cnt"], s["vpos"], s["ppos"], s["apos"],
                                               s["proprios"], s["noise"], self.k, self.v, clip=self.clip,
-                                              prefix=s.get("prefix"), prefix_len=s.get("prefix_len"))
+                                              prefix=s.get("prefix"), prefix_len=s.get("prefix_len"),
+                                              guide=self._guide())
 
-    def load(self, input_ids, pixel_values, cnt, vpos, ppos, apos, proprios, noise, prefix=None, prefix_len=None):
+    def load(self, input_ids, pixel_values, cnt, vpos, ppos, apos, proprios, noise, prefix=None, prefix_len=None,
+             guide_target=None, guide_w=None, guide_coef=None):
         s = self.static
         _load_prefix(s, "prefix", prefix, prefix_len, s["noise"].shape[1])
+        _load_guide(s, guide_target, guide_w, guide_coef)
         s["ids"].copy_(input_ids)
         s["pix"].copy_(pixel_values.reshape(s["pix"].shape))
         s["cnt"].copy_(cnt)
@@ -151,6 +213,11 @@ class ObservationGraph(InferenceGraph):
     the noise; the clamp and the denormalisation are replaced by their prefix forms, the latter copying rows
     ``h < prefix_len[b]`` from ``prev_actions`` bit for bit.
 
+    ``enable_guidance()`` adds ``guide_target`` (what is left of the previous chunk, ROBOT units,
+    normalised inside the graph by ``pz_action_normalize``), ``guide_w``, ``guide_coef`` and ``prefix_len`` (the
+    delay): the loop is the guided one, the clamp skips rows ``h < prefix_len[b]`` and the denormalisation copies them
+    from ``guide_target`` bit for bit -- the robot executes those rows from the old chunk anyway.
+
     The static inputs are the raw ones; the prefix counts are ``attention_mask.sum(1)``, computed by the caller where
     the mask is born, so no [L, L] mask exists on this path, and the position ids are constants.  ``stats`` is the
     dataset-statistics dict (``proprio`` / ``action`` -> ``p01``, ``p99``, ``mean``, ``std``) with the optional keys
@@ -202,6 +269,25 @@ class ObservationGraph(InferenceGraph):
         self.out_norm = None
         self._f8 = None
 
+    def _guide_static(self):
+        InferenceGraph._guide_static(self)
+        s = self.static
+        s["prefix_len"] = torch.zeros(s["noise"].shape[0], device=s["noise"].device, dtype=torch.int32)
+
+    def _run_guided(self, pix, proprios):
+        from . import ops
+
+        s = self.static
+        d = self.m._engine().d
+        target = ops.action_normalize(s["guide_target"], *self.stat["action"], self.modes["action"], n_pass=1)
+        self.out_norm = self.m._engine().infer_action(s["ids"], pix, s["cnt"], s["vpos"], s["ppos"], s["apos"],
+                                                      proprios, s["noise"], self.k, self.v, clip=False,
+                                                      guide=self._guide(target))
+        if self.clip and d.clip is not None:
+            ops.clamp_(self.out_norm, -d.clip, d.clip, prefix_len=s["prefix_len"])
+        return ops.action_denormalize(self.out_norm, *self.stat["action"], self.modes["action"], n_pass=1,
+                                      prev=s["guide_target"], prefix_len=s["prefix_len"])
+
     def _run(self):
         from . import ops
 
@@ -209,6 +295,8 @@ class ObservationGraph(InferenceGraph):
         d = self.m._engine().d
         pix = ops.image_resize_norm(s["frames"], d.img, channels_last=self.channels_last)
         proprios = ops.proprio_normalize(s["raw_proprio"], *self.stat["proprio"], self.modes["proprio"])
+        if self.guidance:
+            return self._run_guided(pix, proprios)
         prefix = None
         if self.prefix:
             prefix = ops.action_normalize(s["prev_actions"], *self.stat["action"], self.modes["action"], n_pass=1)
@@ -218,10 +306,21 @@ class ObservationGraph(InferenceGraph):
         return ops.action_denormalize(self.out_norm, *self.stat["action"], self.modes["action"], n_pass=1,
                                       prev=s.get("prev_actions"), prefix_len=s.get("prefix_len"))
 
-    def load(self, frames, input_ids, cnt, raw_proprio, noise, prev_actions=None, delay=None):
+    def load(self, frames, input_ids, cnt, raw_proprio, noise, prev_actions=None, delay=None, guide_w=None,
+             guide_coef=None):
+        """``guide_w`` / ``guide_coef`` (a guidance graph): ``prev_actions`` is then the guidance target in robot units
+        and ``delay`` the number of leading rows passed through from it"""
         s = self.static
         nb = dict(non_blocking=True)
-        _load_prefix(s, "prev_actions", prev_actions, delay, s["noise"].shape[1], **nb)
+        if self.guidance:
+            _load_guide(s, prev_actions, guide_w, guide_coef, **nb)
+            if delay is None:
+                s["prefix_len"].zero_()
+            else:
+                _load_prefix(s, "guide_target", s["guide_target"], delay, s["noise"].shape[1], **nb)
+        else:
+            _load_guide(s, None, guide_w, guide_coef)
+            _load_prefix(s, "prev_actions", prev_actions, delay, s["noise"].shape[1], **nb)
         s["frames"].copy_(frames.reshape(s["frames"].shape), **nb)
         s["ids"].copy_(input_ids, **nb)
         s["cnt"].copy_(cnt.reshape(s["cnt"].shape), **nb)

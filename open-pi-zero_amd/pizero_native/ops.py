@@ -280,6 +280,30 @@ def linear_dgrad(dy, W, dx, *, beta=False, resid=None, epi=PZ_EPI_NONE, aux=None
     return dx
 
 
+def linear_dgrad_rows(dy, W, dx, *, epi=PZ_EPI_NONE, aux=None, ws=None):
+    """linear_dgrad for a handful of rows (pz_dgrad_rows: M <= 16, N % 8 == 0, K % 8 == 0, PZ_EPI_NONE or
+    PZ_EPI_DGEGLU): W [N, K] is reduced along its rows by every CU, not by the K / 128 workgroups of the 128-tile
+    kernel that pz_gemm plans for a k-strided B.  Returns False, with nothing launched and dx untouched, when the
+    kernel does not take the call -- the caller then runs linear_dgrad.  ws: fp32 scratch (default: the GEMM
+    split-K scratch of the current stream slot)."""
+    M, N = dy.shape
+    K = W.shape[1]
+    if dy.stride(1) != 1 or W.stride(1) != 1 or dx.stride(1) != 1 or (aux is not None and aux.stride(1) != 1):
+        return False
+    need = lib().pz_dgrad_rows_ws_bytes(M, N, K)
+    if ws is None:
+        ws = workspace(dx.device)
+        if ws.numel() * 4 < need:
+            return False
+    rc = lib().pz_dgrad_rows(_p(dy), dy.stride(0), _p(W), W.stride(0), _p(dx), dx.stride(0), M, N, K, int(epi), _p(aux),
+                             0 if aux is None else aux.stride(0), _p(ws), ws.numel() * ws.element_size(), _st())
+    if rc == PZ_ERR_UNSUPPORTED:
+        return False
+    if rc != 0:
+        raise NativeError(f"pz_dgrad_rows failed (rc={rc}): {lib().pz_last_error().decode(errors='replace')}")
+    return True
+
+
 def _split_k(M, N, K):
     """Split the token (reduction) dim when the output has too few 256x256 tiles to fill 256 CUs."""
     tiles = ((N + 255) // 256) * ((K + 255) // 256)
@@ -782,6 +806,32 @@ def euler_step(action, v, ldv, vbs, t, B, H, A, dt, prefix_len=None):
              float(dt), _st())
         return
     call("pz_euler_step", _p(action), _p(v), ldv, vbs, _p(t), B, H, A, float(dt), _st())
+
+
+def _f32c(name, x, shape):
+    assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and tuple(x.shape) == tuple(shape), (
+        f"{name} must be a contiguous fp32 device tensor of shape {tuple(shape)}")
+    return _p(x)
+
+
+def rtc_seed(action, v, ldv, vbs, target, w, t, e, dv, T, row0):
+    """e = w * (target - (action + (1 - t) * v)) (fp32 [B, H, A]) and the backward seed dv [B*T, 8] bf16: bf16(e) in
+    rows row0 .. row0 + H of every sample's T rows, columns < A; zero everywhere else.  v bf16 addressed
+    as euler_step's."""
+    B, H, A = action.shape
+    assert dv.dtype == BF16 and dv.is_contiguous() and tuple(dv.shape) == (B * T, 8), "dv must be bf16 [B*T, 8]"
+    call("pz_rtc_seed", _f32c("action", action, (B, H, A)), _p(v), ldv, vbs, _f32c("target", target, (B, H, A)),
+         _f32c("w", w, (B, H)), _f32c("t", t, (B,)), _f32c("e", e, (B, H, A)), _p(dv), T, row0, B, H, A, _st())
+
+
+def rtc_euler(action, v, ldv, vbs, e, dA, t, coef, k, dt):
+    """g = e + (1 - t) * dA; action += dt * (v + coef[k] * g); t += dt once per sample.  dA bf16 [B*H, >= A]
+    (row-strided), coef fp32 [steps] on the device."""
+    B, H, A = action.shape
+    assert dA.dtype == BF16 and dA.shape[0] == B * H and dA.shape[1] >= A and dA.stride(1) == 1
+    assert coef.dtype == torch.float32 and coef.is_cuda and coef.is_contiguous() and coef.dim() == 1
+    call("pz_rtc_euler", _f32c("action", action, (B, H, A)), _p(v), ldv, vbs, _f32c("e", e, (B, H, A)), _p(dA),
+         dA.stride(0), _f32c("t", t, (B,)), _p(coef), coef.numel(), int(k), B, H, A, float(dt), _st())
 
 
 def action_prefix_init(action, prefix, prefix_len):

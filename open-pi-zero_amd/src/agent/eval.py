@@ -88,23 +88,26 @@ class EvalAgent:
             self._stats = stats
         return self._stats
 
-    def observation_graph(self, bsz, frame_hw, channels_last=True, prefix=False):
-        """the ObservationGraph of one (batch size, frame geometry, layout, with / without an action prefix); built on
-        first use, not yet captured"""
+    def observation_graph(self, bsz, frame_hw, channels_last=True, prefix=False, guidance=False):
+        """the ObservationGraph of one (batch size, frame geometry, layout, with / without an action prefix, with /
+        without guidance); built on first use, not yet captured"""
         from pizero_native.graph import ObservationGraph
 
-        key = (bsz, tuple(int(x) for x in frame_hw), bool(channels_last)) + ((True,) if prefix else ())
+        key = (bsz, tuple(int(x) for x in frame_hw), bool(channels_last)) + ((True,) if prefix else ()) + \
+            (("guide",) if guidance else ())
         g = self._obs_graphs.get(key)
         if g is None:
             g = self._obs_graphs[key] = ObservationGraph(self.model, bsz, key[1], self._dataset_statistics(),
                                                          channels_last=channels_last)
             if prefix:
                 g.enable_prefix()
+            if guidance:
+                g.enable_guidance()
         return g
 
     @torch.no_grad()
     def act(self, frames, input_ids, attention_mask, raw_proprio, noise=None, channels_last=True, prev_actions=None,
-            delay=None):
+            delay=None, overlap=None, guidance_beta=None):
         """Raw observation -> fp32 [B, horizon, action_dim] actions in ROBOT units, one graph replay.
 
         ``frames``: uint8 camera frames of any size, [B (* n_images), H, W, 3] (or [.., 3, H, W] with
@@ -120,7 +123,16 @@ class EvalAgent:
         call runs -- ``prev_actions[:, :delay]``, e.g. from ``src.agent.chunking.next_prefix`` -- and the chunk is
         denoised around them.  Rows >= delay of ``prev_actions`` are ignored.  The returned rows < delay are
         ``prev_actions``' bits.  One capture serves every delay and prefix; calls without ``prev_actions`` keep
-        using the graph without the option."""
+        using the graph without the option.
+
+        ``overlap`` (an int, ``delay <= overlap <= horizon``, ``delay < horizon``) turns the hard prefix
+        into guidance, for checkpoints trained without prefixes: ``prev_actions`` is what is left of the previous
+        chunk (``src.agent.chunking.next_guidance``), its first ``overlap`` rows meaningful, and every Euler step is
+        steered toward them with the weights ``soft_mask(horizon, delay, overlap)`` and the coefficients
+        ``guidance_coef(steps, guidance_beta)`` (``guidance_beta`` defaults to the config key
+        ``action_guidance_beta``, default 5.0).  The returned rows < delay are still ``prev_actions``' bits and the
+        clamp covers the other rows only.  ``overlap=None`` is the hard prefix above, launch for launch; guided calls
+        use a graph of their own, so calls without ``overlap`` keep the graph and the bits they had."""
         self._dataset_statistics()  # without statistics: the ValueError that names the key, before anything else
         m = self.model
         frames, input_ids, attention_mask, raw_proprio = (torch.as_tensor(x) for x in
@@ -146,13 +158,45 @@ class EvalAgent:
                 raise ValueError(f"act: prev_actions must be [B, horizon_steps, action_dim] = "
                                  f"{(B, m.horizon_steps, m.action_dim)}, got {tuple(prev.shape)}")
             kw = dict(prev_actions=prev, delay=delay)
-        g = self.observation_graph(B, hw, channels_last, prefix=bool(kw))
+        if overlap is None and guidance_beta is not None:
+            raise ValueError("act: guidance_beta needs overlap")
+        if overlap is not None:
+            kw.update(self._guidance_tables(kw, B, delay, overlap, guidance_beta))
+        g = self.observation_graph(B, hw, channels_last, prefix=bool(kw) and overlap is None,
+                                   guidance=overlap is not None)
         g.load(frames.contiguous(), input_ids, cnt, raw_proprio.to(torch.float32), noise, **kw)
         if not self.use_graph:
             return g.run_eager()
         if g.graph is None:
             g.capture()
         return g.replay()
+
+    def _guidance_tables(self, kw, B, delay, overlap, beta):
+        """the host-made inputs of a guided call: row weights [B, H] and step coefficients [steps]"""
+        import numpy as np
+
+        from src.agent.chunking import guidance_coef, soft_mask
+
+        m = self.model
+        H = m.horizon_steps
+        if not kw:
+            raise ValueError("act: overlap needs prev_actions and delay")
+        if m.action_expert_adaptive_mode:
+            from pizero_native.engine import GUIDE_ADAPTIVE_MSG
+
+            raise NotImplementedError(GUIDE_ADAPTIVE_MSG)
+        dl = torch.as_tensor(delay)
+        if dl.dtype.is_floating_point or dl.dtype == torch.bool or dl.is_cuda:
+            raise ValueError("act: with overlap, delay must be host integers (an int or [B])")
+        dl = [int(x) for x in (dl.expand(B) if dl.dim() == 0 else dl.reshape(B)).tolist()]
+        overlap = int(overlap)
+        if not all(0 <= x <= overlap <= H and x < H for x in dl):
+            raise ValueError(f"act: need 0 <= delay <= overlap <= horizon_steps = {H} and delay < horizon_steps, got "
+                             f"delay {dl}, overlap {overlap}")
+        if beta is None:
+            beta = cfg_get(self.cfg, "action_guidance_beta", 5.0)
+        w = np.stack([soft_mask(H, x, overlap) for x in dl])
+        return dict(guide_w=torch.from_numpy(w), guide_coef=torch.from_numpy(guidance_coef(m.num_inference_steps, beta)))
 
     def run(self):
         try:

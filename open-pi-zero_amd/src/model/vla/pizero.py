@@ -657,8 +657,12 @@ class PiZero(nn.Module, NoSyncBase):
     def infer_action(self, input_ids, pixel_values, image_text_proprio_mask, action_mask, vlm_position_ids,
                      proprio_position_ids, action_position_ids, proprios, noise: Optional[torch.Tensor] = None,
                      clip: bool = True, prefix_actions: Optional[torch.Tensor] = None,
-                     prefix_len: Optional[torch.Tensor] = None):
+                     prefix_len: Optional[torch.Tensor] = None, guide=None):
         """pizero.py:416-490: prefill caches vlm+proprio K/V once, 10 Euler steps on the action expert.
+        ``guide`` = (target [B, horizon, action_dim] in normalised units, w [B, horizon], coef [steps]) (DESIGN 7i;
+        src/agent/chunking.py: next_guidance, soft_mask, guidance_coef): every Euler step is steered toward the rows
+        of the previous chunk by the denoiser's vector-Jacobian product -- inference-time real-time chunking, for
+        checkpoints trained without a prefix.  Returned in fp32.  It does not compose with a hard prefix.
         ``prefix_actions`` [B, horizon, action_dim] (normalised units) with ``prefix_len`` (ints [B]): the
         first prefix_len[b] actions of the chunk are committed -- returned bit for bit (fp32), the rest denoised
         around them; rows of ``prefix_actions`` past prefix_len[b] are ignored.
@@ -686,6 +690,11 @@ class PiZero(nn.Module, NoSyncBase):
                                  f"{(B, self.horizon_steps, self.action_dim)}, got {tuple(pa.shape)}")
             kw = dict(prefix=pa, prefix_len=self._prefix_len(prefix_len, B))
             dtype = torch.float32  # the committed rows come back bit for bit
+        if guide is not None:
+            if len(guide) != 3:
+                raise ValueError("infer_action: guide is (target, w, coef)")
+            kw["guide"] = tuple(torch.as_tensor(x).to(dev, torch.float32).contiguous() for x in guide)
+            dtype = torch.float32
         a = self._engine().infer_action(
             input_ids.to(dev, torch.int64).contiguous(), pixel_values.to(dev, torch.bfloat16).contiguous(),
             spec, vlm_position_ids.to(dev, torch.int64).contiguous(),
@@ -697,7 +706,7 @@ class PiZero(nn.Module, NoSyncBase):
     @torch.no_grad()
     def infer_action_naive(self, input_ids, pixel_values, causal_mask, vlm_position_ids, proprio_position_ids,
                            action_position_ids, proprios, noise: Optional[torch.Tensor] = None, clip: bool = True,
-                           prefix_actions=None, prefix_len=None):
+                           prefix_actions=None, prefix_len=None, guide=None):
         """pizero.py:492-557.  Re-running the prefix every step gives identical math (the vlm/proprio rows
         never attend to actions), so the native path reuses the cached prefix (fp32-exact equivalence:
         SURVEY 8(c) measured |naive - cached| = 1.8e-7).  With an adaLN expert only the vlm rows are cached: the
@@ -705,6 +714,9 @@ class PiZero(nn.Module, NoSyncBase):
         if prefix_actions is not None or prefix_len is not None:
             raise NotImplementedError("infer_action_naive takes no action prefix (prefix_actions / prefix_len, DESIGN "
                                       "7f): use infer_action")
+        if guide is not None:
+            raise NotImplementedError("infer_action_naive takes no action guidance (guide / action_guidance_beta, "
+                                      "DESIGN 7i): use infer_action")
         itp, amask = self.split_full_mask_into_submasks(causal_mask)
         return self.infer_action(input_ids, pixel_values, itp, amask, vlm_position_ids, proprio_position_ids,
                                  action_position_ids, proprios, noise=noise, clip=clip)
