@@ -704,6 +704,30 @@ int pz_rtc_euler(float* action, const void* v, int64_t ldv, int64_t v_bstride, c
                  int64_t ldda, float* t, const float* coef, int64_t steps, int64_t k, int64_t B, int64_t H, int64_t A,
                  float dt, void* stream);
 
+/* 4-bit base weights of QLoRA (quantize: True; csrc/pz_q4.hip).  Entry points added under ABI 22.
+ * The format is tests/quant4_ref.py's, bit for bit: blocks of 64 elements, codes into the 16-entry fp4 / nf4 table
+ * (two per byte, the even element in the high nibble), one scale per block, itself stored as a uint8 code into the
+ * 256-entry dynamic map with one fp32 nested_absmax per 256 blocks and one fp32 offset per tensor.
+ *   pz_q4_quantize: w bf16 [n] -> packed uint8 [n / 2], absmax fp32 [ceil(n / 64)].  n must be even: an odd n is
+ *                   refused on the host before any launch (nothing is written).
+ *   pz_q4_dequant:  dst bf16 [n] = bf16(fp16(table[nibble] * (qmap[absmax_codes[i / 64]] * nested_absmax[i / 16384]
+ *                   + offset))).  packed 4-byte aligned, dst 16-byte aligned, qmap fp32 [256] on the device.
+ *   pz_q4_dequant_multi: 1..PZ_Q4_MAX_SEGS weights in one launch (the q|k|v and gate|up sites), one table and map. */
+enum { PZ_Q4_FP4 = 0, PZ_Q4_NF4 = 1 };
+#define PZ_Q4_MAX_SEGS 4
+typedef struct pz_q4_seg {
+  const void* packed;
+  const void* absmax_codes;
+  const float* nested_absmax;
+  void* dst;
+  int64_t n;
+  float offset;
+} pz_q4_seg;
+int pz_q4_quantize(const void* w, void* packed, float* absmax, int64_t n, int32_t table, void* stream);
+int pz_q4_dequant(const void* packed, const void* absmax_codes, const float* nested_absmax, float offset,
+                  const float* qmap, int32_t table, int64_t n, void* dst, void* stream);
+int pz_q4_dequant_multi(const pz_q4_seg* segs, int32_t count, const float* qmap, int32_t table, void* stream);
+
 /* test instrument: fill every CU's LDS with `word` (0xffffffff = NaN) on `stream`, so the next kernel's reads of
  * LDS it did not write return NaN (tests/test_train_loop_gpu.py; _lib.call runs it before every launch under
  * PZ_POISON_LDS=1).  Not on any product path. */

@@ -22,15 +22,16 @@ BUILD = os.path.join(HERE, "build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 SOURCES = ["pz_gemm.hip", "pz_gemm_host.hip", "pz_gemm_rows.hip", "pz_gemm_tall.hip", "pz_norm.hip", "pz_attn.hip", "pz_misc.hip", "pz_flash.hip", "pz_optim.hip", "pz_optim_r.hip", "pz_gemv.hip", "pz_decode.hip", "pz_expert_attn.hip", "pz_quant.hip", "pz_adaln.hip", "pz_lora.hip", "pz_avg.hip", "pz_obs.hip", "pz_augment.hip", "pz_episodes.hip", "pz_dgrad_rows.hip",
-           "pz_rtc.hip"]
+           "pz_rtc.hip", "pz_q4.hip"]
 HEADERS = [os.path.join(CSRC, "pz_common.h"), os.path.join(CSRC, "pz_decode_kernels.h"), os.path.join(CSRC, "pz_gemm_epi.h"), os.path.join(CSRC, "pz_gemm_plan.h"), os.path.join(ROOT, "include", "pz_abi.h")]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result",
          "-Wno-unused-value", "-munsafe-fp-atomics"]
 # per-file extra flags: the 8-bit optimizer is held bit-exact to its float32 oracle, so no FMA contraction; the
 # weight-averaging lerp is held bit-exact to torch.lerp (its two FMAs are explicit); the guidance kernels are held
-# bit-exact to a float32 restatement that rounds every multiply and add
+# bit-exact to a float32 restatement that rounds every multiply and add, and so are the 4-bit (de)quantisation kernels
 FILE_FLAGS = {"pz_optim.hip": ["-ffp-contract=off"], "pz_optim_r.hip": ["-ffp-contract=off"],
-              "pz_avg.hip": ["-ffp-contract=off"], "pz_rtc.hip": ["-ffp-contract=off"]}
+              "pz_avg.hip": ["-ffp-contract=off"], "pz_rtc.hip": ["-ffp-contract=off"],
+              "pz_q4.hip": ["-ffp-contract=off"]}
 # sources that include another source: pz_optim_r.hip is pz_optim.hip's second object (the rounding entry points)
 FILE_DEPS = {"pz_optim_r.hip": ["pz_optim.hip"]}
 

@@ -51,6 +51,13 @@ class GemmArgs(C.Structure):
     ]
 
 
+PZ_Q4_FP4, PZ_Q4_NF4, PZ_Q4_MAX_SEGS = 0, 1, 4  # include/pz_abi.h
+
+
+class Q4Seg(C.Structure):
+    _fields_ = [("packed", vp), ("absmax_codes", vp), ("nested_absmax", vp), ("dst", vp), ("n", i64), ("offset", f32)]
+
+
 class SmallGemmArgs(C.Structure):
     _fields_ = [
         ("M", i64), ("N", i64), ("K", i64),
@@ -234,6 +241,10 @@ SIGNATURES = {
     "pz_dgrad_rows": [vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, vp, i64, vp, i64, vp],
     "pz_rtc_seed": [vp, vp, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp],
     "pz_rtc_euler": [vp, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, f32, vp],
+    # 4-bit base weights of QLoRA (csrc/pz_q4.hip)
+    "pz_q4_quantize": [vp, vp, vp, i64, i32, vp],
+    "pz_q4_dequant": [vp, vp, vp, f32, vp, i32, i64, vp, vp],
+    "pz_q4_dequant_multi": [vp, i32, vp, i32, vp],
     "pz_debug_poison_lds": [C.c_uint32, vp],
     "pz_debug_spin": [i64, i64, vp],
     "pz_last_error": [],

@@ -14,6 +14,11 @@ Consequences, all MI355X-first:
   * every parameter starts on a 16-byte boundary (vector loads).
 nn.Parameters of the module tree are rebound to views of the arena, so
 state_dict()/load_state_dict()/named_parameters() keep the reference keys.
+
+``side`` (quantize: True): the named slots -- the base weights that are packed to 4 bits -- are laid out in
+the same order in a buffer of their own (``side``), so fused spans stay adjacent, load_state_dict and by-name fills
+work as ever, and ``drop_side()`` releases every one of them at once after packing.  They have no place in ``data``,
+hence none in the gradient arena, the optimizer spans or the DDP buckets.  Without side slots the layout is unchanged.
 """
 
 from __future__ import annotations
@@ -33,6 +38,7 @@ class Slot:
     offset: int
     numel: int
     region: str
+    side: bool = False  # offset counts in Arena.side, not Arena.data
 
 
 def _round(n, a=ALIGN):
@@ -42,38 +48,56 @@ def _round(n, a=ALIGN):
 class Arena:
     """Owns the flat buffers; maps reference parameter names to views."""
 
-    def __init__(self, entries, device, dtype):
+    def __init__(self, entries, device, dtype, side=frozenset(), alloc_side=True):
         # entries: list of (name, shape, region, param-or-None) in layout order
         self.slots: dict[str, Slot] = {}
         self.order: list[str] = []
         self.region_range: dict[str, list[int]] = {}
-        off = 0
+        off = soff = 0
         for name, shape, region, _ in entries:
             n = 1
             for s in shape:
                 n *= int(s)
-            self.slots[name] = Slot(name, tuple(int(s) for s in shape), off, n, region)
             self.order.append(name)
+            if name in side:
+                self.slots[name] = Slot(name, tuple(int(s) for s in shape), soff, n, region, True)
+                soff += _round(n)
+                continue
+            self.slots[name] = Slot(name, tuple(int(s) for s in shape), off, n, region)
             r = self.region_range.setdefault(region, [off, off])
             r[1] = off + n
             off += _round(n)
         self.total = _round(off, 64)
+        self.side_total = _round(soff, 64)
         self.data = torch.zeros(self.total, device=device, dtype=dtype)
+        self.side = torch.zeros(self.side_total, device=device, dtype=dtype) if soff and alloc_side else None
         self.grad = None
         for name, _, _, p in entries:
-            if p is not None and p.device.type != "meta":
+            if p is not None and p.device.type != "meta" and not (self.slots[name].side and self.side is None):
                 self.view(name).copy_(p.detach())
+
+    def drop_side(self):
+        """release the side buffer (its slots were packed to 4 bits); views of it must be gone first"""
+        self.side = None
 
     # ------------------------------------------------------------------ views
     def view(self, name, buf=None):
         s = self.slots[name]
-        b = self.data if buf is None else buf
+        b = self._buf(s, name) if buf is None else buf
         return b[s.offset : s.offset + s.numel].view(s.shape)
+
+    def _buf(self, slot, name):
+        if not slot.side:
+            return self.data
+        if self.side is None:
+            raise RuntimeError(f"{name} is packed to 4 bits (quantize: True): it has no bf16 storage")
+        return self.side
 
     def span(self, first, last, buf=None, rows=None):
         """2-D view over adjacent slots first..last (same trailing dim)."""
         a, z = self.slots[first], self.slots[last]
-        b = self.data if buf is None else buf
+        assert a.side == z.side, f"{first}..{last} spans two buffers"
+        b = self._buf(a, first) if buf is None else buf
         cols = a.shape[-1] if len(a.shape) > 1 else 1
         n = z.offset + z.numel - a.offset
         assert n % cols == 0
@@ -103,11 +127,13 @@ class Arena:
     def bind(self, params: dict):
         """Rebind nn.Parameters (name -> (module, attr, requires_grad)) to arena views."""
         for name, (mod, attr, rg) in params.items():
-            if name not in self.slots:
-                continue
+            if name not in self.slots or (self.slots[name].side and self.side is None):
+                continue  # not in this arena, or packed to 4 bits (the module holds the packed tensor)
             mod._parameters[attr] = nn.Parameter(self.view(name), requires_grad=rg)
 
     def apply(self, fn):
         self.data = fn(self.data)
+        if self.side is not None:
+            self.side = fn(self.side)
         if self.grad is not None:
             self.grad = fn(self.grad)

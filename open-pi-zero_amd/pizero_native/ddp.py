@@ -132,7 +132,8 @@ def region_marks(model):
     marks = {}
 
     def end_of(names):
-        return max(ar.slots[n].offset + ar.slots[n].numel for n in names if n in ar.slots)
+        # (4-bit base weights live in the arena's side buffer: in no bucket)
+        return max(ar.slots[n].offset + ar.slots[n].numel for n in names if n in ar.slots and not ar.slots[n].side)
 
     nL = model.joint_model.num_hidden_layers
     head = ["action_decoder.weight", "action_decoder.bias", "joint_model.mixtures.action.norm.weight"]

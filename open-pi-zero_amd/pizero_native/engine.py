@@ -322,11 +322,12 @@ class LoraSite:
 
 
 def _merged_weights(fn):
-    """Inference entry point of a LoRA model: refresh the merged shadow weights and read them in place of the base"""
+    """Inference entry point of a LoRA or 4-bit model: refresh the merged shadow weights and read them in place of the
+    base"""
 
     @functools.wraps(fn)
     def wrap(self, *a, **k):
-        if not self.m.has_lora:
+        if not self._shadow_w:
             return fn(self, *a, **k)
         if not torch.cuda.is_current_stream_capturing():
             self.lora_refresh()
@@ -404,6 +405,14 @@ class Engine:
         self._merged = None
         self._merged_ver = None
         self._infer = False
+        # 4-bit base weights (quantize: True): the packed store; training dequantises a site's weights into
+        # one scratch buffer right before the GEMM that reads them (forward and input gradient), inference reads the
+        # shadow, which for these weights is laid out like the arena's side buffer
+        self._q4 = model._q4
+        self._q4_w = frozenset(self._q4.w) if self._q4 is not None else frozenset()
+        self._shadow_w = self._lora_w | self._q4_w
+        self._merged_side = None
+        self._q4_buf = None
         # the guided denoise step runs the training backward of the expert rows for the input gradient
         # alone: while set, no weight gradient, column sum, norm-weight partial or hook notification is launched
         # (rg() answers False, requires_grad is not touched) and no adapter site is used (the merged weights are read)
@@ -436,10 +445,31 @@ class Engine:
         return self.m._arena
 
     def w(self, name):
+        if name in self._q4_w:
+            return self.span(name, name).view(self.ar.slots[name].shape)
         return self.ar.view(name, self._merged if self._infer and name in self._lora_w else None)
 
     def span(self, first, last):
+        if first in self._q4_w:
+            return self.ar.span(first, last, self._merged_side) if self._infer else self._q4_dequant(first, last)
         return self.ar.span(first, last, self._merged if self._infer and first in self._lora_w else None)
+
+    def _q4_dequant(self, first, last):
+        """The bf16 weights of the adjacent 4-bit slots first..last, dequantised into the scratch buffer by one
+        pz_q4_dequant launch: the [rows, in] view Arena.span gives of a bf16 span -- same shape, contiguous, 16-byte
+        aligned.  One scratch (sized for the largest fused site) serves every site: a site's GEMM is enqueued before
+        the next site's dequantisation on the same stream; only the vlm group reads these weights, and it never runs
+        on the side stream (_on), nor do the data-parallel hooks read a weight."""
+        ar = self.ar
+        names = ar.order[ar.order.index(first): ar.order.index(last) + 1]
+        a, z = ar.slots[first], ar.slots[last]
+        n = z.offset + z.numel - a.offset
+        assert sum(self._q4.w[nm].n for nm in names) == n, f"{first}..{last}: padding inside a 4-bit span"
+        if self._q4_buf is None or self._q4_buf.device != ar.data.device:
+            most = max(sum(ar.slots[f"{pre}{pr}.weight"].numel for pr in projs)
+                       for pre, projs in self.m._vlm_linear_sites())
+            self._q4_buf = torch.empty(most, device=ar.data.device, dtype=BF16)
+        return self._q4.dequant(names, self._q4_buf).view(n // a.shape[-1], a.shape[-1])
 
     # --------------------------------------------------------------- LoRA --
     def lora(self, *wnames):
@@ -496,21 +526,32 @@ class Engine:
         so they come back bit for bit after any train -> infer -> train sequence and state_dict() always holds the
         unmerged tensors.  Rebuilt in place (captured graphs keep their pointers) when the weight version changed.
         Returns True if it rebuilt."""
-        if not self._lora_w:
+        if not self._shadow_w:
             return False
         ver = self.weights_version()
-        if self._merged is not None and self._merged_ver == ver and self._merged.device == self.ar.data.device:
+        dev = self.ar.data.device
+        main = bool(self._lora_w - self._q4_w)  # adapted bf16 weights: their shadow has the arena's layout
+        stale = lambda need, buf: need and (buf is None or buf.device != dev)  # noqa: E731
+        if self._merged_ver == ver and not stale(main, self._merged) and not stale(self._q4_w, self._merged_side):
             return False
         from src.model.lora import LORA_SCALING
 
-        if self._merged is None or self._merged.device != self.ar.data.device:
+        if stale(main, self._merged):
             self._merged = torch.empty_like(self.ar.data)
-        for wn in sorted(self._lora_w):
-            W = self.ar.view(wn)
+        if stale(self._q4_w, self._merged_side):
+            # 4-bit base: the shadow is the only bf16 copy of these weights, allocated at the first inference call
+            self._merged_side = torch.empty(self.ar.side_total, device=dev, dtype=BF16)
+        for wn in sorted(self._shadow_w):
+            q4 = wn in self._q4_w
+            dst = self.ar.view(wn, self._merged_side if q4 else self._merged)
+            if wn not in self._lora_w:  # quantize without adapters: the shadow is dequant(W4)
+                self._q4.dequant([wn], dst.view(-1))
+                continue
+            W = self._q4_dequant(wn, wn).view(dst.shape) if q4 else self.ar.view(wn)  # 4-bit: through the scratch
             A = self.ar.view(wn[: -len("weight")] + "lora_A")
             Bm = self.ar.view(wn[: -len("weight")] + "lora_B")
             out, inn = W.shape
-            ops.gemm(out, inn, A.shape[0], Bm, A.shape[0], True, A, inn, False, self.ar.view(wn, self._merged), inn,
+            ops.gemm(out, inn, A.shape[0], Bm, A.shape[0], True, A, inn, False, dst, inn,
                      alpha=LORA_SCALING, resid=W, ld_resid=inn)
         self._merged_ver = ver
         return True

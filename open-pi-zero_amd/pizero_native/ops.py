@@ -23,6 +23,7 @@ from ._lib import (
     PZ_OBS_MAX_TAPS,
     PZ_OBS_NORM_BOUND,
     PZ_OBS_NORM_GAUSSIAN,
+    PZ_Q4_MAX_SEGS,
     PZ_SUMSQ_PARTS,
     AdamW8Args,
     QkvRopeArgs,
@@ -30,6 +31,7 @@ from ._lib import (
     ExpertAttnBwdArgs,
     FlashArgs,
     GemmArgs,
+    Q4Seg,
     SmallGemmArgs,
     NativeError,
     SoftmaxArgs,
@@ -1292,6 +1294,42 @@ def episode_gather_rows(action, proprio, episode_of, episode_offsets, tokens, id
          _p(dev_idx), N, E, A, P, L, B, Wn, Hn, int(pad_id), _p(out["action"]), _p(out["proprio"]),
          _p(out["action_pad_mask"]), _p(out["input_ids"]), _p(out["attention_mask"]), _st())
     return out
+
+
+# ---- 4-bit base weights of QLoRA (csrc/pz_q4.hip) --------------------------------------------------------
+Q4_TABLES = {"fp4": 0, "nf4": 1}  # include/pz_abi.h PZ_Q4_FP4 / PZ_Q4_NF4
+
+
+def _q4_table(qtype):
+    if qtype not in Q4_TABLES:
+        raise ValueError(f"quantize_type must be fp4 or nf4, got {qtype!r}")
+    return Q4_TABLES[qtype]
+
+
+def q4_quantize(w, packed, absmax, qtype="fp4"):
+    """packed uint8 [n / 2] (the even element in the high nibble) and the fp32 absmax of every block of 64 of the
+    flat bf16 tensor ``w`` (n = w.numel(), even: an odd n is refused before any launch)."""
+    n = w.numel()
+    assert w.dtype == BF16 and w.is_cuda and w.is_contiguous(), "w must be a contiguous bf16 device tensor"
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() >= n // 2
+    assert absmax.dtype == torch.float32 and absmax.is_contiguous() and absmax.numel() >= (n + 63) // 64
+    call("pz_q4_quantize", _p(w), _p(packed), _p(absmax), n, _q4_table(qtype), _st())
+
+
+def q4_dequant(segs, qmap, qtype="fp4"):
+    """dst[:n] = the bf16 weights of every (packed, absmax_codes, nested_absmax, offset, n, dst) of ``segs`` (1 to
+    PZ_Q4_MAX_SEGS weights, one launch); qmap: the fp32 [256] dynamic map on the device."""
+    assert 1 <= len(segs) <= PZ_Q4_MAX_SEGS, f"1..{PZ_Q4_MAX_SEGS} segments per launch"
+    assert qmap.dtype == torch.float32 and qmap.is_cuda and qmap.is_contiguous() and qmap.numel() == 256
+    arr = (Q4Seg * len(segs))()
+    for a, (packed, codes, nam, offset, n, dst) in zip(arr, segs):
+        assert packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() >= n // 2
+        assert codes.dtype == torch.uint8 and codes.is_contiguous() and codes.numel() >= (n + 63) // 64
+        assert nam.dtype == torch.float32 and nam.is_contiguous() and nam.numel() >= ((n + 63) // 64 + 255) // 256
+        assert dst.dtype == BF16 and dst.is_contiguous() and dst.numel() >= n
+        a.packed, a.absmax_codes, a.nested_absmax, a.dst, a.n, a.offset = (_p(packed), _p(codes), _p(nam), _p(dst),
+                                                                           int(n), float(offset))
+    call("pz_q4_dequant_multi", C.cast(arr, C.c_void_p), len(segs), _p(qmap), _q4_table(qtype), _st())
 
 
 def debug_poison_lds(word=0xFFFFFFFF):

@@ -30,6 +30,7 @@ class EvalAgent:
             self.load_checkpoint(cfg_get(cfg, "checkpoint_path"))
         self.model.tie_action_proprio_weights()
         self.model.freeze_all_weights()
+        self.model.quantize_base_()  # quantize: True packs the VLM's Linears (no-op otherwise, or if loaded packed)
         self.model.eval()
         self.use_graph = use_graph
         self._graphs = {}

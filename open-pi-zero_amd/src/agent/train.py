@@ -123,10 +123,15 @@ class TrainAgent:
         self.micro_batches_seen = 0
         self.wandb_id = None
         self.lora = bool(cfg_get(cfg, "lora", False))
-        if cfg_get(cfg, "quantize", False):
-            raise NotImplementedError("quantize: True (4-bit bitsandbytes) is not supported; use lora: True alone")
+        # quantize: True (QLoRA): the frozen base Linears of the VLM are packed to 4 bits after loading
+        self.quantize = bool(cfg_get(cfg, "quantize", False))
         if self.lora and not cfg_get(cfg, "load_pretrained_weights", False):  # train.py:87-89
             raise AssertionError("lora: True must be used with load_pretrained_weights: True")
+        if self.quantize and not cfg_get(cfg, "load_pretrained_weights", False):  # train.py:87-89
+            raise AssertionError("quantize: True must be used with load_pretrained_weights: True")
+        if self.quantize and (cfg_get(cfg, "use_ema", False) or cfg_get(cfg, "use_swa", False)):
+            raise NotImplementedError("quantize: True with use_ema / use_swa is not supported: the average would need "
+                                      "a second copy of the packed base weights")
         model = PiZero(cfg, use_ddp=self.multi_gpu, device=self.device, dtype=self.dtype, init="default")
         self.model = model
         self._averaging_enabled = bool(cfg_get(cfg, "use_ema", False) or cfg_get(cfg, "use_swa", False))
@@ -140,6 +145,7 @@ class TrainAgent:
         model.freeze_unused_weights()
         if self.lora:  # train.py:101-102
             model.freeze_non_lora_weights_in_vlm()
+        model.quantize_base_()  # no-op without quantize: True
         self.model_meta = PiZeroDDP(model) if self.multi_gpu else model
         # every rank keeps its own average: the weights are identical across ranks, so nothing is communicated
         self.model_averaging = ModelAveraging(model, cfg, self.device)
@@ -155,7 +161,8 @@ class TrainAgent:
             dataset = self._episode_batches("train", per_dev)
         self.train_dataloader = dataset if dataset is not None else SyntheticBridgeDataset(cfg, per_dev, seed=self.rank)
 
-        self.train_vlm = bool(cfg_get(cfg, "train_vlm", True))
+        # quantize without lora: the VLM is fully frozen (the model logged the reference's warning, train.py:90-93)
+        self.train_vlm = bool(cfg_get(cfg, "train_vlm", True)) and not (self.quantize and not self.lora)
         # the reference's bnb AdamW8bit (train.py:171-175): blockwise 8-bit state by default
         self.state_bits = int(cfg_get(cfg, "optimizer_state_bits", 8))
         # how the fp32 update becomes the bf16 weight (FusedAdamW): nearest | compensated | stochastic

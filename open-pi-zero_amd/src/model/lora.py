@@ -6,8 +6,10 @@ lora_B [out, r]) so state_dict keys and shapes match; ``y = x W^T (+ bias) + s (
 the native engine adds the adapter term inside the GEMM (pz_gemm's rank extension), computes the adapter
 gradients with pz_lora_wgrad and runs inference on merged weights (pizero_native.engine).
 
-Out of scope, each refused with the config key in the message: ``quantize: True`` (4-bit bitsandbytes) and
-``lora_dropout > 0``.
+``quantize: True`` (the reference's Linear4bit / LoRALinear4bit, QLoRA) builds the same containers: the base weight
+is constructed and loaded in bf16 and ``PiZero.quantize_base_()`` packs it to 4 bits afterwards.
+
+Out of scope, refused with the config key in the message: ``lora_dropout > 0``.
 """
 
 from __future__ import annotations
@@ -31,10 +33,8 @@ class LoRALinear(nn.Linear):
 
 
 def lora_rank(config, use_quantize: bool, use_lora: bool) -> int:
-    """0 without LoRA, else config.lora.r; refuses the two unsupported settings by name"""
-    if use_quantize:
-        raise NotImplementedError("quantize: True (use_quantize, 4-bit bitsandbytes QLoRA) is not supported; "
-                                  "use lora: True without quantize")
+    """0 without LoRA, else config.lora.r; refuses lora_dropout > 0 by name.  use_quantize changes nothing here: the
+    4-bit packing is PiZero's (quantize_base_), which also refuses a VLM quantised only in part."""
     if not use_lora:
         return 0
     r = int(cfg_get(config, "lora.r"))

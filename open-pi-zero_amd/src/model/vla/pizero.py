@@ -128,6 +128,8 @@ class PiZero(nn.Module, NoSyncBase):
                 raise ValueError(f"mixture.{mix}.adaptive_mode must equal action_expert_adaptive_mode "
                                  f"({self.action_expert_adaptive_mode!r})")
         ada = bool(self.action_expert_adaptive_mode)
+        self._q4_type = self._quantize_type(cfg)  # None: bf16 base weights
+        self._q4 = None  # pizero_native.quant4.Q4Store once quantize_base_() packed them
         with torch.device("meta"):
             self.embed_tokens = nn.Embedding(self.vocab_size, self.image_text_hidden_size, self.pad_token_id)
             self.vision_tower = instantiate(cfg_get(cfg, "vision"))
@@ -145,6 +147,32 @@ class PiZero(nn.Module, NoSyncBase):
         self._eng = None
         self._kv = None
         self._build_arena(torch.device(device or "cpu"), dtype or torch.float32, init=init)
+        if self._q4_type and not self.has_lora:  # the reference's warning (train.py:90-93)
+            log.warning("Quantizing VLM but not adding Lora weights, which means the VLM will be fully frozen!")
+            for part in (self.vision_tower, self.multi_modal_projector, self.joint_model.mixtures["vlm"]):
+                for p in part.parameters():
+                    p.requires_grad = False
+
+    @staticmethod
+    def _quantize_type(cfg):
+        """quantize: True -> "fp4" | "nf4" (``quantize_type``, default fp4), else None.  The 4-bit set is
+        every Linear of SigLIP, the projector and the vlm mixture, so the three ``use_quantize`` copies the reference's
+        config derives from ``quantize`` must agree, and the expert mixtures stay bf16."""
+        keys = ("vision.use_quantize", "vision_projector.use_quantize", "joint.config.mixture.vlm.use_quantize")
+        flags = [bool(cfg_get(cfg, k, False)) for k in keys]
+        if any(flags) and not all(flags):
+            raise NotImplementedError("use_quantize is set for " + ", ".join(k for k, f in zip(keys, flags) if f)
+                                      + " but not for " + ", ".join(k for k, f in zip(keys, flags) if not f)
+                                      + ": a partly quantised VLM is not supported, set quantize for all three")
+        for mix in ("proprio", "action"):
+            if cfg_get(cfg, f"joint.config.mixture.{mix}.use_quantize", False):
+                raise NotImplementedError(f"mixture.{mix}.use_quantize: the action expert stays bf16; quantize covers "
+                                          "SigLIP, the projector and the vlm mixture")
+        if not all(flags):
+            return None
+        from pizero_native.quant4 import check_qtype
+
+        return check_qtype(cfg_get(cfg, "quantize_type", "fp4") or "fp4")
 
     # ================================================================ arena ==
     def _layout(self):
@@ -212,28 +240,36 @@ class PiZero(nn.Module, NoSyncBase):
         from src.model.lora import LoRALinear
 
         out = []
-
-        def site(prefix, projs):
+        for prefix, projs in self._vlm_linear_sites():
             mod, _ = _resolve(self, prefix + projs[0] + ".weight")
             if isinstance(mod, LoRALinear):
                 out.extend((f"{prefix}{pr}.lora_A", "lora") for pr in projs)
                 out.extend((f"{prefix}{pr}.lora_B", "lora") for pr in projs)
+        return out
 
+    def _vlm_linear_sites(self):
+        """(prefix, projections) of every Linear site of SigLIP, the projector and the vlm mixture, fused sites as
+        one entry, in backward-completion order: the sites that take LoRA adapters and (quantize: True) 4-bit weights"""
         nL = self.joint_model.num_hidden_layers
         for l in reversed(range(nL)):
             p = f"joint_model.mixtures.vlm.layers.{l}."
-            site(p + "mlp.", ["down_proj"])
-            site(p + "mlp.", ["gate_proj", "up_proj"])
-            site(p + "self_attn.", ["o_proj"])
-            site(p + "self_attn.", ["q_proj", "k_proj", "v_proj"])
-        site("multi_modal_projector.", ["linear"])
+            yield p + "mlp.", ["down_proj"]
+            yield p + "mlp.", ["gate_proj", "up_proj"]
+            yield p + "self_attn.", ["o_proj"]
+            yield p + "self_attn.", ["q_proj", "k_proj", "v_proj"]
+        yield "multi_modal_projector.", ["linear"]
         vt = "vision_tower.vision_model.encoder.layers."
         for i in reversed(range(len(self.vision_tower.vision_model.encoder.layers))):
-            site(f"{vt}{i}.mlp.", ["fc2"])
-            site(f"{vt}{i}.mlp.", ["fc1"])
-            site(f"{vt}{i}.self_attn.", ["out_proj"])
-            site(f"{vt}{i}.self_attn.", ["q_proj", "k_proj", "v_proj"])
-        return out
+            yield f"{vt}{i}.mlp.", ["fc2"]
+            yield f"{vt}{i}.mlp.", ["fc1"]
+            yield f"{vt}{i}.self_attn.", ["out_proj"]
+            yield f"{vt}{i}.self_attn.", ["q_proj", "k_proj", "v_proj"]
+
+    def _q4_names(self):
+        """names of the base weights that quantize: True packs to 4 bits, in arena order"""
+        if not self._q4_type:
+            return []
+        return [f"{prefix}{pr}.weight" for prefix, projs in self._vlm_linear_sites() for pr in projs]
 
     @property
     def has_lora(self):
@@ -246,9 +282,10 @@ class PiZero(nn.Module, NoSyncBase):
         for name, region in self._layout():
             mod, attr = _resolve(self, name)
             p = mod._parameters[attr]
-            entries.append((name, tuple(p.shape), region, p))
+            packed = self._q4 is not None and name in self._q4.w  # the module holds uint8 [n / 2, 1]
+            entries.append((name, self._q4.w[name].shape if packed else tuple(p.shape), region, p))
             binds[name] = (mod, attr, p.requires_grad)
-        self._arena = Arena(entries, device, dtype)
+        self._arena = Arena(entries, device, dtype, side=frozenset(self._q4_names()), alloc_side=self._q4 is None)
         self._arena.bind(binds)
         self._tie_lm_head()
         self._pmap = {name: _resolve(self, name) for name, _ in self._layout()}
@@ -296,6 +333,9 @@ class PiZero(nn.Module, NoSyncBase):
             return super()._apply(fn, recurse)
         rg = {n: self._pmap[n][0]._parameters[self._pmap[n][1]].requires_grad for n in self._pmap}
         self._arena.apply(fn)
+        if self._q4 is not None:
+            self._q4.apply(fn)
+            self._bind_packed()
         self._arena.bind({n: (m, a, rg[n]) for n, (m, a) in self._pmap.items()})
         self._tie_lm_head()
         self._eng = None
@@ -343,10 +383,113 @@ class PiZero(nn.Module, NoSyncBase):
 
             if self._arena.data.device.type != "cuda":
                 raise RuntimeError("PiZero runs on the MI355X HIP path only: move the model to a GPU (.to('cuda'))")
+            self.quantize_base_()
             self._eng = Engine(self)
             if getattr(self, "_fp8_infer", False):
                 self._eng.prepare_fp8()
         return self._eng
+
+    # ============================================================ 4-bit base ==
+    @property
+    def quantized(self):
+        return bool(self._q4_type)
+
+    @torch.no_grad()
+    def quantize_base_(self):
+        """quantize: True: pack every Linear weight of SigLIP, the projector and the vlm mixture to 4 bits
+        (pz_q4_quantize + the nested step) and release their bf16 storage.  Called by TrainAgent / EvalAgent after the
+        weights are loaded and by the first forward otherwise; a no-op without ``quantize`` and when already packed.
+        Afterwards ``module.weight`` is the packed uint8 [n / 2, 1] tensor (bitsandbytes' Params4bit layout) and
+        state_dict() carries the packed state; loading a bf16 ``weight`` quantises it."""
+        if not self._q4_type or self._q4 is not None:
+            return self
+        ar = self._arena
+        if ar.data.device.type != "cuda":
+            raise RuntimeError("quantize_base_ runs the HIP quantiser: move the model to a GPU first (.to('cuda'))")
+        if ar.data.dtype != torch.bfloat16:
+            raise RuntimeError("quantize_base_ packs bf16 weights: call model.to(torch.bfloat16) first")
+        from pizero_native.quant4 import Q4Store
+
+        store = Q4Store(self._q4_type, ar.data.device)
+        for n in self._q4_names():
+            store.quantize(n, ar.view(n))
+        self._q4 = store
+        self._bind_packed()
+        ar.drop_side()
+        self._q4_changed()
+        return self
+
+    def _bind_packed(self):
+        for n, q in self._q4.w.items():
+            mod, attr = self._pmap[n]
+            mod._parameters[attr] = nn.Parameter(q.packed.view(-1, 1), requires_grad=False)
+
+    def _q4_changed(self):
+        """the packed weights changed: everything keyed on the weight version (merged shadow, fp8 codes) is stale"""
+        from torch.autograd.graph import increment_version
+
+        increment_version(self._arena.data)
+        if self._eng is not None and self._eng._q4 is not self._q4:
+            self._eng = None
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        """nn.Module.state_dict; a packed Linear emits ``weight`` (uint8 [n / 2, 1]) followed by weight.absmax,
+        weight.quant_map, weight.nested_absmax, weight.nested_quant_map and the weight.quant_state.bitsandbytes__*
+        JSON blob -- the packed layout of bitsandbytes 0.45 as far as it can be restated without the package"""
+        sd = super().state_dict(*args, destination=destination, prefix=prefix, keep_vars=keep_vars)
+        if self._q4 is None:
+            return sd
+        items = list(sd.items())
+        sd.clear()
+        for k, v in items:
+            sd[k] = v
+            n = k[len(prefix):]
+            if n in self._q4.w:
+                for suf, t in self._q4.entries(n).items():
+                    if suf:
+                        sd[k + suf] = t if keep_vars else t.detach()
+        return sd
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        """nn.Module.load_state_dict.  With quantize: True a packed ``weight`` (uint8, with its weight.* tensors) is
+        installed without requantising and a floating-point ``weight`` is quantised on load (before quantize_base_()
+        it is simply copied, like every other tensor)."""
+        if not self._q4_type:
+            return super().load_state_dict(state_dict, strict=strict, assign=assign)
+        qn = set(self._q4_names())
+        sd, packed_in, float_in = {}, {}, {}
+        for k, v in state_dict.items():
+            base = k.split(".weight", 1)[0] + ".weight" if ".weight." in k else k
+            if base in qn and (k != base or v.dtype == torch.uint8):
+                packed_in.setdefault(base, {})[k[len(base):]] = v
+            elif base in qn and self._q4 is not None:
+                float_in[base] = v
+            else:
+                sd[k] = v
+        if packed_in:
+            self.quantize_base_()
+            # quantize_base_ packed whatever the arena held; floating-point weights of this load are packed below
+            float_in.update({k: sd.pop(k) for k in list(sd) if k in qn})
+        handled = set(packed_in) | set(float_in)
+        if handled:
+            dev = self._arena.data.device
+            for n, ent in packed_in.items():
+                self._q4.install(n, self._arena.slots[n].shape, ent, dev)
+            for n, v in float_in.items():
+                shape = self._arena.slots[n].shape
+                if tuple(v.shape) != tuple(shape):
+                    raise RuntimeError(f"size mismatch for {n}: copying a param with shape {tuple(v.shape)} from "
+                                       f"checkpoint, the shape in current model is {tuple(shape)}")
+                self._q4.quantize(n, v.to(device=dev, dtype=torch.bfloat16).contiguous())
+            self._bind_packed()
+            self._q4_changed()
+        res = super().load_state_dict(sd, strict=False, assign=assign)
+        missing = [k for k in res.missing_keys if k not in handled]
+        if strict and (missing or res.unexpected_keys):
+            raise RuntimeError("Error(s) in loading state_dict for PiZero: missing keys "
+                               f"{missing}, unexpected keys {list(res.unexpected_keys)}")
+        res.missing_keys[:] = missing
+        return res
 
     def use_fp8_inference(self, enabled: bool = True):
         """Config C5 (BASELINE.json configs[4], "fp8 MFMA attention/MLP"): run inference (infer_action,
