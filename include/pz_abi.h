@@ -355,6 +355,17 @@ typedef struct pz_expert_attn_bwd_args {
 int pz_expert_attn_fwd(const pz_decode_attn_args* a, float* lse, void* stream);
 int64_t pz_expert_attn_bwd_ws_bytes(int64_t B, int64_t rows, int64_t nk, int64_t nkeys);
 int pz_expert_attn_bwd(const pz_expert_attn_bwd_args* a, void* stream);
+/* Several flow draws per observation (flow_samples_per_observation): the two entry points above with the
+ * keys of a pair split over two buffers.  a->B counts (observation, draw) pairs e.  Key rows j < a->prefix are read
+ * from a->k / a->v at batch e / kv_group (the VLM rows, written once per observation, read-only); key rows
+ * j >= a->prefix from k_own / v_own + e*own_bstride + (j - a->prefix)*256 (bf16, the pair's own proprio and action
+ * keys, compact).  Mask (cnt[e] per pair), soft cap, softmax, launches, workspace, lse and the dq / dk / dv layout
+ * (per pair) are those of pz_expert_attn_fwd / _bwd; with kv_group 1 and the own rows equal to rows prefix.. of k / v
+ * the outputs have the same bits.  kv_group >= 1, B % kv_group == 0, 0 <= prefix <= nk. */
+int pz_expert_attn_fwd_shared(const pz_decode_attn_args* a, const void* k_own, const void* v_own, int64_t own_bstride,
+                              int64_t kv_group, float* lse, void* stream);
+int pz_expert_attn_bwd_shared(const pz_expert_attn_bwd_args* a, const void* k_own, const void* v_own,
+                              int64_t own_bstride, int64_t kv_group, void* stream);
 
 /* SigLIP patch embed im2col (siglip.py:42-48,69-74): pixels bf16 [B,3,H,W] -> cols bf16
  * [B*(H/ps)*(W/ps), ldc] with k = c*ps*ps + ky*ps + kx, zero pad k in [3*ps*ps, ldc) */

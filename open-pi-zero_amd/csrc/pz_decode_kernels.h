@@ -15,9 +15,16 @@
 // Shared by pz_decode.hip (pz_decode_attn, LSE = false) and pz_expert_attn.hip (pz_expert_attn_fwd, LSE = true: the
 // same launches also write the fp32 log-sum-exp m + log(l) of every query row, lse[b*T*nh + t*nh + h], for the
 // frozen-VLM training backward).  O has the same bits in both instantiations.
+//
+// SHARED (pz_expert_attn_fwd_shared / _bwd_shared, several flow draws per observation): the batch index counts
+// (observation, draw) pairs e; key rows j < prefix are read from a.k / a.v at batch e / group (the VLM rows, written
+// once per observation), key rows j >= prefix from the pair's own compact buffers at row j - prefix.  Every load picks
+// its buffer per lane after the clamp to nk - 1, so a tile or chunk that straddles prefix reads both.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
+
+#include <type_traits>
 
 #include "pz_common.h"
 
@@ -28,6 +35,24 @@ constexpr int DA_R = 32;     // query rows per row tile (tokens x heads)
 constexpr int DA_RMAX = 1024;  // query rows per sample
 constexpr int DA_HD = 256;   // head dim (Gemma)
 constexpr int DA_RS = DA_HD + 4;  // workspace row: O[256], m, l (16-byte aligned rows)
+
+// own keys of the SHARED form: k / v + e * bstride + (j - prefix) * 256 for key rows j >= prefix of pair e; the
+// rows j < prefix come from batch e / group of the shared buffers
+struct da_own {
+  const bf16_t* k;
+  const bf16_t* v;
+  int64_t bstride, group;
+};
+struct da_no_own {};
+template <bool SHARED>
+using da_own_t = std::conditional_t<SHARED, da_own, da_no_own>;
+
+// K or V row of key (already clamped to nk - 1): the shared buffer below prefix P, the pair's own buffer from P on
+template <bool SHARED>
+__device__ __forceinline__ const bf16_t* da_kv_row(const bf16_t* base, const bf16_t* own, int key, int P) {
+  if (SHARED && key >= P) return own + (int64_t)(key - P) * DA_HD;
+  return base + (int64_t)key * DA_HD;
+}
 
 __device__ __forceinline__ bool da_allowed(int t, int j, int nk, int cnt, int P, int C) {
   if (j >= nk) return false;
@@ -105,8 +130,8 @@ __device__ __forceinline__ bf16x8 da_vfrag(const char* img, int dt, int lane) {
   return __builtin_bit_cast(bf16x8, out);
 }
 
-template <bool LSE>
-__global__ void __launch_bounds__(256) decode_attn_mfma(pz_decode_attn_args a, int nch, float* lse) {
+template <bool LSE, bool SHARED = false>
+__global__ void __launch_bounds__(256) decode_attn_mfma(pz_decode_attn_args a, int nch, float* lse, da_own_t<SHARED> own) {
   __shared__ float S[DA_R][DA_KC + 1];
   __shared__ __attribute__((aligned(16))) bf16_t Pm[DA_R][DA_KC + 8];  // bf16 probabilities [row][key]
   __shared__ __attribute__((aligned(16))) char Vimg[DA_KC * 512];       // one chunk of V, transposed reads
@@ -118,8 +143,16 @@ __global__ void __launch_bounds__(256) decode_attn_mfma(pz_decode_attn_args a, i
   const int grp = blockIdx.x, b = blockIdx.y / rtiles, rt = blockIdx.y % rtiles, r0 = rt * DA_R;
   const bool masked = a.cnt != nullptr;
   const int cnt = masked ? a.cnt[b] : nk;
-  const bf16_t* K = (const bf16_t*)a.k + (int64_t)b * a.k_bstride;
-  const bf16_t* V = (const bf16_t*)a.v + (int64_t)b * a.v_bstride;
+  int64_t kvb = b;  // batch of the K / V rows (SHARED: the pair's observation)
+  const bf16_t *Ko = nullptr, *Vo = nullptr;
+  if constexpr (SHARED) {
+    kvb = b / (int)own.group;
+    Ko = own.k + (int64_t)b * own.bstride;
+    Vo = own.v + (int64_t)b * own.bstride;
+  }
+  const int P = (int)a.prefix;
+  const bf16_t* K = (const bf16_t*)a.k + kvb * a.k_bstride;
+  const bf16_t* V = (const bf16_t*)a.v + kvb * a.v_bstride;
   const int nchunks = (nk + DA_KC - 1) / DA_KC;
   const int c0 = grp * nch, c1 = min(nchunks, c0 + nch);
   const int g = lane >> 4;
@@ -137,7 +170,7 @@ __global__ void __launch_bounds__(256) decode_attn_mfma(pz_decode_attn_args a, i
   }
   auto load_k = [&](int c, bf16x8 (&kf)[8]) {
     const int key = min(c * DA_KC + kt * 16 + (lane & 15), nk - 1);
-    const bf16_t* kp = K + (int64_t)key * DA_HD + 8 * g;
+    const bf16_t* kp = da_kv_row<SHARED>(K, Ko, key, P) + 8 * g;
 #pragma unroll
     for (int dc = 0; dc < 8; ++dc) kf[dc] = *reinterpret_cast<const bf16x8*>(kp + dc * 32);
   };
@@ -146,7 +179,7 @@ __global__ void __launch_bounds__(256) decode_attn_mfma(pz_decode_attn_args a, i
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = threadIdx.x + i * 256, kr = e >> 5, ch = e & 31;
-      vv[i] = *reinterpret_cast<const u32x4*>(V + (int64_t)min(c * DA_KC + kr, nk - 1) * DA_HD + 8 * ch);
+      vv[i] = *reinterpret_cast<const u32x4*>(da_kv_row<SHARED>(V, Vo, min(c * DA_KC + kr, nk - 1), P) + 8 * ch);
     }
   };
   const float inv_cap = a.cap > 0.f ? 1.f / a.cap : 0.f;
@@ -181,7 +214,7 @@ __global__ void __launch_bounds__(256) decode_attn_mfma(pz_decode_attn_args a, i
         const int kl = kt * 16 + 4 * g + e;
         float x = sv[e] * a.scale;
         if (a.cap > 0.f) x = a.cap * tanh_fast(x * inv_cap);
-        const bool ok = rok && (masked ? da_allowed(qt, j0 + kl, nk, cnt, (int)a.prefix, (int)a.cond) : j0 + kl < nk);
+        const bool ok = rok && (masked ? da_allowed(qt, j0 + kl, nk, cnt, P, (int)a.cond) : j0 + kl < nk);
         S[row - r0][kl] = ok ? x : -INFINITY;
       }
     }
@@ -279,10 +312,26 @@ inline void da_grouping(int nchunks, int64_t tiles, int& nch, int& ngroups) {
   ngroups = (nchunks + nch - 1) / nch;
 }
 
-// argument checks + the two launches of pz_decode_attn / pz_expert_attn_fwd
-template <bool LSE>
-int da_launch(const pz_decode_attn_args* a, float* lse, void* stream) {
+// checks of the own-key arguments of the SHARED entry points (B pairs, nk keys of which the first prefix are shared)
+inline int da_check_own(const char* what, const void* k_own, const void* v_own, int64_t own_bstride, int64_t kv_group,
+                        int64_t B, int64_t nk, int64_t prefix) {
+  PZ_CHECK_ARG(kv_group >= 1, "%s: kv_group must be >= 1", what);
+  PZ_CHECK_ARG(B % kv_group == 0, "%s: B (pairs) must be a multiple of kv_group", what);
+  PZ_CHECK_ARG(prefix >= 0 && prefix <= nk, "%s: prefix must lie in [0, nk]", what);
+  PZ_CHECK_ARG(nk == prefix || (k_own && v_own && PZ_ALIGNED(k_own, 16) && PZ_ALIGNED(v_own, 16) &&
+                                own_bstride % 8 == 0 && own_bstride >= (nk - prefix) * DA_HD),
+               "%s: k_own / v_own NULL, misaligned, or own_bstride below (nk - prefix) * 256", what);
+  return PZ_OK;
+}
+
+// argument checks + the two launches of pz_decode_attn / pz_expert_attn_fwd / pz_expert_attn_fwd_shared
+template <bool LSE, bool SHARED = false>
+int da_launch(const pz_decode_attn_args* a, float* lse, void* stream, da_own_t<SHARED> own = {}) {
   PZ_CHECK_ARG(a && a->q && a->k && a->v && a->o && a->ws && a->B > 0 && a->nh > 0, "decode_attn: bad args");
+  if constexpr (SHARED) {
+    const int rc = da_check_own("expert_attn_fwd_shared", own.k, own.v, own.bstride, own.group, a->B, a->nk, a->prefix);
+    if (rc != PZ_OK) return rc;
+  }
   PZ_CHECK_ARG(!LSE || (lse && PZ_ALIGNED(lse, 4)), "expert_attn_fwd: lse is NULL or misaligned");
   PZ_CHECK_ARG(a->head_dim == DA_HD && a->T >= 1 && a->T * a->nh <= DA_RMAX && a->nk >= 1,
                "decode_attn: head_dim 256 and tokens x heads <= 1024 query rows per sample");
@@ -305,8 +354,8 @@ int da_launch(const pz_decode_attn_args* a, float* lse, void* stream) {
     nch = (nchunks + 1) / 2;
     ngroups = (nchunks + nch - 1) / nch;
   }
-  hipLaunchKernelGGL(decode_attn_mfma<LSE>, dim3((unsigned)ngroups, (unsigned)(a->B * rtiles)), dim3(256), 0, st, *a,
-                     nch, lse);
+  hipLaunchKernelGGL((decode_attn_mfma<LSE, SHARED>), dim3((unsigned)ngroups, (unsigned)(a->B * rtiles)), dim3(256), 0,
+                     st, *a, nch, lse, own);
   PZ_CHECK_LAUNCH();
   if (ngroups == 1) return PZ_OK;  // the kernel wrote O
   hipLaunchKernelGGL(decode_attn_combine<LSE>, dim3((unsigned)(a->T * a->nh), (unsigned)a->B), dim3(256), 0, st, *a,

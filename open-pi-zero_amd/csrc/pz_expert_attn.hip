@@ -15,6 +15,11 @@
 //                        expert_attn_merge_dq / _dkv sum the partials in fixed order and write bf16.
 // No atomics: two launches on the same inputs give the same bits.  Keys >= nk are never loaded (sources clamp to
 // nk - 1, their p and dS are 0); dK / dV rows outside [key0, key0 + nkeys) are not written.
+//
+//   pz_expert_attn_fwd_shared / pz_expert_attn_bwd_shared   the same kernels instantiated with SHARED (several flow
+//                        draws per observation): the batch counts (observation, draw) pairs, key rows
+//                        below prefix come from the observation's K / V (read-only, one copy for all its draws), the
+//                        rest from the pair's own compact buffers; dq / dk / dv are written per pair as above.
 #include "pz_decode_kernels.h"
 
 namespace {
@@ -51,8 +56,9 @@ inline eb_ws eb_layout(int64_t B, int64_t rows, int64_t nkeys, int ngroups) {
 }
 
 // grid (ngroups, B * rtiles), 256 threads
+template <bool SHARED>
 __global__ void __launch_bounds__(256) expert_attn_bwd_tile(pz_expert_attn_bwd_args a, int nch, int64_t ws_dk,
-                                                            int64_t ws_dv) {
+                                                            int64_t ws_dv, da_own_t<SHARED> own) {
   __shared__ __attribute__((aligned(16))) char Kimg[DA_KC * 512];  // one chunk of K
   __shared__ __attribute__((aligned(16))) char Qimg[DA_R * 512];   // the row tile's Q
   __shared__ __attribute__((aligned(16))) char Gimg[DA_R * 512];   // the row tile's dO
@@ -66,8 +72,16 @@ __global__ void __launch_bounds__(256) expert_attn_bwd_tile(pz_expert_attn_bwd_a
   const int grp = blockIdx.x, b = blockIdx.y / rtiles, rt = blockIdx.y % rtiles, r0 = rt * DA_R;
   const bool masked = a.cnt != nullptr;
   const int cnt = masked ? a.cnt[b] : nk;
-  const bf16_t* K = (const bf16_t*)a.k + (int64_t)b * a.k_bstride;
-  const bf16_t* V = (const bf16_t*)a.v + (int64_t)b * a.v_bstride;
+  int64_t kvb = b;  // batch of the K / V rows (SHARED: the pair's observation)
+  const bf16_t *Ko = nullptr, *Vo = nullptr;
+  if constexpr (SHARED) {
+    kvb = b / (int)own.group;
+    Ko = own.k + (int64_t)b * own.bstride;
+    Vo = own.v + (int64_t)b * own.bstride;
+  }
+  const int P = (int)a.prefix;
+  const bf16_t* K = (const bf16_t*)a.k + kvb * a.k_bstride;
+  const bf16_t* V = (const bf16_t*)a.v + kvb * a.v_bstride;
   const int nchunks = (nk + DA_KC - 1) / DA_KC;
   const int c0 = grp * nch, c1 = min(nchunks, c0 + nch);
   const int key0 = (int)a.key0, key1 = (int)(a.key0 + a.nkeys);
@@ -126,12 +140,13 @@ __global__ void __launch_bounds__(256) expert_attn_bwd_tile(pz_expert_attn_bwd_a
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = threadIdx.x + i * 256, kr = e >> 5, ch = e & 31;
-      eb_stage(Kimg, kr, ch, *reinterpret_cast<const u32x4*>(K + (int64_t)min(j0 + kr, nk - 1) * DA_HD + 8 * ch));
+      eb_stage(Kimg, kr, ch,
+               *reinterpret_cast<const u32x4*>(da_kv_row<SHARED>(K, Ko, min(j0 + kr, nk - 1), P) + 8 * ch));
     }
     {  // S^T and dP^T tiles, then p and dS
       const int key = min(j0 + kt * 16 + (lane & 15), nk - 1);
-      const bf16_t* kp = K + (int64_t)key * DA_HD + 8 * g;
-      const bf16_t* vp = V + (int64_t)key * DA_HD + 8 * g;
+      const bf16_t* kp = da_kv_row<SHARED>(K, Ko, key, P) + 8 * g;
+      const bf16_t* vp = da_kv_row<SHARED>(V, Vo, key, P) + 8 * g;
       f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int dc = 0; dc < 8; ++dc) {
@@ -148,7 +163,7 @@ __global__ void __launch_bounds__(256) expert_attn_bwd_tile(pz_expert_attn_bwd_a
           tv = tanh_fast(x * inv_cap);
           lg = a.cap * tv;
         }
-        const bool ok = rok && (masked ? da_allowed(qt, j0 + kl, nk, cnt, (int)a.prefix, (int)a.cond) : j0 + kl < nk);
+        const bool ok = rok && (masked ? da_allowed(qt, j0 + kl, nk, cnt, P, (int)a.cond) : j0 + kl < nk);
         const float p = ok ? __expf(lg - my_lse) : 0.f;
         ds[e] = ok ? a.scale * (1.f - tv * tv) * p * (dp[e] - my_delta) : 0.f;
         dST_s[kl][rl] = f2bf(ds[e]);
@@ -231,10 +246,6 @@ __global__ void __launch_bounds__(256) expert_attn_merge_dkv(pz_expert_attn_bwd_
 
 }  // namespace
 
-extern "C" int pz_expert_attn_fwd(const pz_decode_attn_args* a, float* lse, void* stream) {
-  return da_launch<true>(a, lse, stream);
-}
-
 extern "C" int64_t pz_expert_attn_bwd_ws_bytes(int64_t B, int64_t rows, int64_t nk, int64_t nkeys) {
   const int nchunks = (int)((nk + DA_KC - 1) / DA_KC);
   int nch, ngroups;
@@ -242,9 +253,17 @@ extern "C" int64_t pz_expert_attn_bwd_ws_bytes(int64_t B, int64_t rows, int64_t 
   return eb_layout(B, rows, nkeys, ngroups).total * (int64_t)sizeof(float);
 }
 
-extern "C" int pz_expert_attn_bwd(const pz_expert_attn_bwd_args* a, void* stream) {
+namespace {
+
+// argument checks + the three launches of pz_expert_attn_bwd / pz_expert_attn_bwd_shared
+template <bool SHARED>
+int eb_launch(const pz_expert_attn_bwd_args* a, void* stream, da_own_t<SHARED> own) {
   PZ_CHECK_ARG(a && a->q && a->k && a->v && a->o && a->dO && a->lse && a->dq && a->dk && a->dv && a->ws && a->B > 0 &&
                    a->nh > 0, "expert_attn_bwd: bad args");
+  if constexpr (SHARED) {
+    const int rc = da_check_own("expert_attn_bwd_shared", own.k, own.v, own.bstride, own.group, a->B, a->nk, a->prefix);
+    if (rc != PZ_OK) return rc;
+  }
   PZ_CHECK_ARG(a->head_dim == DA_HD && a->T >= 1 && a->T * a->nh <= DA_RMAX && a->nk >= 1,
                "expert_attn_bwd: head_dim 256 and tokens x heads <= 1024 query rows per sample");
   PZ_CHECK_ARG(a->key0 >= 0 && a->nkeys >= 1 && a->key0 + a->nkeys <= a->nk,
@@ -264,8 +283,8 @@ extern "C" int pz_expert_attn_bwd(const pz_expert_attn_bwd_args* a, void* stream
   da_grouping(nchunks, a->B * rtiles, nch, ngroups);
   const eb_ws w = eb_layout(a->B, rows, a->nkeys, ngroups);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(expert_attn_bwd_tile, dim3((unsigned)ngroups, (unsigned)(a->B * rtiles)), dim3(256), 0, st, *a, nch,
-                     w.dk, w.dv);
+  hipLaunchKernelGGL(expert_attn_bwd_tile<SHARED>, dim3((unsigned)ngroups, (unsigned)(a->B * rtiles)), dim3(256), 0, st,
+                     *a, nch, w.dk, w.dv, own);
   PZ_CHECK_LAUNCH();
   hipLaunchKernelGGL(expert_attn_merge_dq, dim3((unsigned)rows, (unsigned)a->B), dim3(256), 0, st, *a, ngroups);
   PZ_CHECK_LAUNCH();
@@ -273,4 +292,24 @@ extern "C" int pz_expert_attn_bwd(const pz_expert_attn_bwd_args* a, void* stream
                      (int)rtiles, w.dk, w.dv);
   PZ_CHECK_LAUNCH();
   return PZ_OK;
+}
+
+}  // namespace
+
+extern "C" int pz_expert_attn_fwd(const pz_decode_attn_args* a, float* lse, void* stream) {
+  return da_launch<true>(a, lse, stream);
+}
+
+extern "C" int pz_expert_attn_fwd_shared(const pz_decode_attn_args* a, const void* k_own, const void* v_own,
+                                         int64_t own_bstride, int64_t kv_group, float* lse, void* stream) {
+  return da_launch<true, true>(a, lse, stream, da_own{(const bf16_t*)k_own, (const bf16_t*)v_own, own_bstride, kv_group});
+}
+
+extern "C" int pz_expert_attn_bwd(const pz_expert_attn_bwd_args* a, void* stream) {
+  return eb_launch<false>(a, stream, da_no_own{});
+}
+
+extern "C" int pz_expert_attn_bwd_shared(const pz_expert_attn_bwd_args* a, const void* k_own, const void* v_own,
+                                         int64_t own_bstride, int64_t kv_group, void* stream) {
+  return eb_launch<true>(a, stream, da_own{(const bf16_t*)k_own, (const bf16_t*)v_own, own_bstride, kv_group});
 }

@@ -174,6 +174,8 @@ SIGNATURES = {
     "pz_expert_attn_fwd": [C.POINTER(DecodeAttnArgs), vp, vp],
     "pz_expert_attn_bwd_ws_bytes": [i64, i64, i64, i64],
     "pz_expert_attn_bwd": [C.POINTER(ExpertAttnBwdArgs), vp],
+    "pz_expert_attn_fwd_shared": [C.POINTER(DecodeAttnArgs), vp, vp, i64, i64, vp, vp],
+    "pz_expert_attn_bwd_shared": [C.POINTER(ExpertAttnBwdArgs), vp, vp, i64, i64, vp],
     "pz_attn_softmax": [C.POINTER(SoftmaxArgs), vp],
     "pz_attn_softmax_bwd": [vp, vp, i64, vp, vp, i64, i64, i64, f32, f32, vp],
     "pz_flash_fwd": [C.POINTER(FlashArgs), vp],

@@ -190,6 +190,10 @@ FP8_ADAPTIVE_MSG = ("fp8 inference is not available with action_expert_adaptive_
 PREFIX_ADAPTIVE_MSG = ("an action prefix (action_prefix_max_delay / prefix_len, DESIGN 7f) is not available with "
                        "action_expert_adaptive_mode (adaLN / adaLN-Zero): the adaLN condition is one time per sample, "
                        "and a prefix row needs its own (time 1)")
+DRAWS_FROZEN_MSG = ("flow_samples_per_observation > 1 (several flow draws per observation, DESIGN 7k) needs the "
+                    "frozen-VLM pass: nothing trainable in the VLM (train_vlm: False, no trainable adapters) and the "
+                    "Pi0 block mask, because the draws share one forward-only VLM prefill and the joint attention "
+                    "kernels would need the VLM rows' dK / dV from every draw")
 
 
 # inference-time guidance toward the previous chunk: what it does not combine with, by config key
@@ -1142,13 +1146,15 @@ class Engine:
         self._jkv_holder = weakref.ref(tok)
         return kv
 
-    def _pre_attn_train(self, g, l, X, pos, st, Qj, Kj, Vj, dev, ada=None, Lq=None, qoff=None):
+    def _pre_attn_train(self, g, l, X, pos, st, Qj, Kj, Vj, dev, ada=None, Lq=None, qoff=None, Lk=None, koff=None):
         """One group's input RMSNorm + q|k|v projection + RoPE + joint Q / K / V scatter of joint layer l
         (paligemma/modules.py:7-21, mixture.py:162-215, joint_model.py:170-257).  Lq / qoff: Qj holds Lq query tokens
-        per sample and the group's start at qoff (default: all L joint tokens, the group at g.off)."""
+        per sample and the group's start at qoff (default: all L joint tokens, the group at g.off).  Lk / koff: Kj / Vj
+        hold Lk key rows per sample and the group's start at koff (default: the Lp joint rows, the group at g.off)."""
         d = self.d
-        L, Lp, nh, hd = d.L if Lq is None else Lq, d.Lp, d.nh, d.hd
+        L, Lp, nh, hd = d.L if Lq is None else Lq, d.Lp if Lk is None else Lk, d.nh, d.hd
         qoff = g.off if qoff is None else qoff
+        koff = g.off if koff is None else koff
         B = Qj.shape[0]
         p = f"{g.prefix}{l}."
         x = X[g.name]
@@ -1162,11 +1168,11 @@ class Engine:
             # Q / K / V (N1: no [M, 2560] qkv tensor, no split launch); rows too few for the 8-phase
             # kernel (the action expert's 320) take GEMM + qkv_rope_split (same bits)
             if not (self.fuse_qkv_rope and ops.gemm_qkv_rope(h, W, pos[g.name], self.rope(g.theta), Qj, Kj, Vj, g.T,
-                                                             nh, hd, L, qoff, Lp, g.off, lora=lora)):
+                                                             nh, hd, L, qoff, Lp, koff, lora=lora)):
                 qkv = torch.empty(M, (nh + 2) * hd, device=dev, dtype=BF16)
                 ops.linear(h, W, qkv, lora=lora)
                 ops.qkv_rope_split(qkv, pos[g.name], self.rope(g.theta), Qj, Kj, Vj, B, g.T, nh, 1, hd, L, qoff, Lp,
-                                   g.off)
+                                   koff)
 
         u = self._linear(h, [p + f"self_attn.{k}_proj.weight" for k in "qkv"], self.qkv_w(p), None, True, gemm=proj)
         st["g"][g.name] = {"x": x, "h": h, "r": r, "u_qkv": u}
@@ -1341,17 +1347,20 @@ class Engine:
         dO[g.name] = o
         dXm[g.name] = dxm
 
-    def _qkv_backward(self, g, gs, p, dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta, nh, hd, dev, A=None, l=None, qoff=None):
+    def _qkv_backward(self, g, gs, p, dQ, dK, dV, dX, dXm, pos, B, L, Lp, beta, nh, hd, dev, A=None, l=None, qoff=None,
+                      koff=None):
         """One group's q|k|v projection + input RMSNorm backward of a joint layer (mixture.py:162-215,
         joint_model.py:170-257 + inverse RoPE): dQ / dK / dV rows of the group -> dX[g].  dQ holds L query tokens per
-        sample, the group's from qoff (default g.off)."""
+        sample, the group's from qoff (default g.off); dK / dV hold Lp key rows per sample, the group's from koff
+        (default g.off)."""
         qoff = g.off if qoff is None else qoff
+        koff = g.off if koff is None else koff
         x = gs["x"]
         M = x.shape[0]
         W = (nh + 2) * hd
         dqkv = torch.empty(M, W, device=dev, dtype=BF16)
         ops.qkv_rope_split_bwd(None if gs.get("skip") else dQ, dK, dV, pos[g.name], self.rope(g.theta), dqkv,
-                               B, g.T, nh, 1, hd, L, qoff, Lp, g.off)
+                               B, g.T, nh, 1, hd, L, qoff, Lp, koff)
         names = [p + f"self_attn.{k}_proj.weight" for k in "qkv"]
         rgs = [self.rg(n) for n in names]
         dh = torch.empty(M, g.hid, device=dev, dtype=BF16)
@@ -1517,11 +1526,16 @@ class Engine:
         attention path on the expert's query rows"""
         return self.d.hd == 256 and T * self.d.nh <= 1024
 
-    def _expert_layers_train(self, groups, X, pos, cnt, B, save, Kall, Vall):
+    def _expert_layers_train(self, groups, X, pos, cnt, B, save, Kall, Vall, draws=1):
         """The expert groups' joint layers against the K/V rows [0, P) that the forward-only VLM pass left in
         Kall / Vall [nL, B, Lp, hd]: their q|k|v epilogue scatters their K/V into rows [P, P + T), their T * nh query
         rows per sample attend to all L keys (pz_expert_attn_fwd: O + log-sum-exp; outside its limits the GEMM path
-        with its P / tanh exports on those rows), their activations are saved as in _joint_layers_train."""
+        with its P / tanh exports on those rows), their activations are saved as in _joint_layers_train.
+
+        draws > 1 (several flow draws per observation): B and cnt count (observation, draw) pairs, every
+        row-wise stage runs on them unchanged, and Kall / Vall stay [nL, B / draws, Lp, hd].  A pair's own K/V go to
+        compact [B, T, hd] buffers per layer and pz_expert_attn_fwd_shared reads rows [0, P) from the pair's
+        observation; the GEMM path copies those rows into per-pair [B, Lp, hd] buffers first and runs as above."""
         d = self.d
         dev = X[groups[0].name].device
         L, Lp, nh, hd, P = d.L, d.Lp, d.nh, d.hd, d.P
@@ -1535,13 +1549,33 @@ class Engine:
             last = l == d.nL - 1
             Qe = torch.empty(B, T, W, device=dev, dtype=BF16)
             Kj, Vj = Kall[l], Vall[l]
+            if draws > 1 and not kern:  # per-pair copies of the observation's rows [0, P); pad rows zero
+                Ks, Vs = Kj, Vj
+                Kj = torch.zeros(B, Lp, hd, device=dev, dtype=BF16)
+                Vj = torch.zeros(B, Lp, hd, device=dev, dtype=BF16)
+                for s in range(draws):
+                    ops.copy_rows(Ks, hd, Lp * hd, Kj[s:], hd, draws * Lp * hd, B // draws, P, hd)
+                    ops.copy_rows(Vs, hd, Lp * hd, Vj[s:], hd, draws * Lp * hd, B // draws, P, hd)
             st = {"Q": Qe, "K": Kj, "V": Vj, "g": {}}
+            if draws > 1 and kern:
+                Ko = torch.empty(B, T, hd, device=dev, dtype=BF16)
+                Vo = torch.empty(B, T, hd, device=dev, dtype=BF16)
+                st["Ko"], st["Vo"] = Ko, Vo
             for g in groups:
-                self._pre_attn_train(g, l, X, pos, st, Qe, Kj, Vj, dev, ada, Lq=T, qoff=g.off - P)
+                if draws > 1 and kern:
+                    self._pre_attn_train(g, l, X, pos, st, Qe, Ko, Vo, dev, ada, Lq=T, qoff=g.off - P, Lk=T,
+                                         koff=g.off - P)
+                else:
+                    self._pre_attn_train(g, l, X, pos, st, Qe, Kj, Vj, dev, ada, Lq=T, qoff=g.off - P)
             if kern:
                 Oall = torch.empty(B * T, W, device=dev, dtype=BF16)
                 lse = torch.empty(B, T * nh, device=dev, dtype=F32)
-                ops.expert_attn_fwd(Qe, T, 0, Kj, Vj, Oall, lse, B, nh, T, L, 1.0 / math.sqrt(hd), 50.0, cnt, P, d.C, P)
+                if draws > 1:
+                    ops.expert_attn_fwd_shared(Qe, T, 0, Kj, Vj, Ko, Vo, draws, Oall, lse, B, nh, T, L,
+                                               1.0 / math.sqrt(hd), 50.0, cnt, P, d.C, P)
+                else:
+                    ops.expert_attn_fwd(Qe, T, 0, Kj, Vj, Oall, lse, B, nh, T, L, 1.0 / math.sqrt(hd), 50.0, cnt, P,
+                                        d.C, P)
                 st["lse"], st["Oall"] = lse, Oall
                 if len(groups) == 1:
                     Os = {groups[0].name: Oall}
@@ -1567,10 +1601,11 @@ class Engine:
         save["joint"] = layers
         return X
 
-    def _expert_layers_backward(self, groups, dX, pos, cnt, B, sv, beta):
+    def _expert_layers_backward(self, groups, dX, pos, cnt, B, sv, beta, draws=1):
         """Backward of _expert_layers_train: per layer the expert groups' MLP / o_proj backward, the attention backward
         for their query rows (pz_expert_attn_bwd: dQ and the dK / dV of key rows [P, P + T) only; outside its limits
-        the backward GEMMs on those rows), and their q|k|v backward.  Nothing is computed for the VLM rows."""
+        the backward GEMMs on those rows), and their q|k|v backward.  Nothing is computed for the VLM rows.
+        draws > 1: B and cnt count pairs; pz_expert_attn_bwd_shared writes dK / dV into compact [B, T, hd] buffers."""
         d = self.d
         L, Lp, nh, hd, P = d.L, d.Lp, d.nh, d.hd, d.P
         dev = next(v for v in dX.values() if v is not None).device
@@ -1582,8 +1617,10 @@ class Engine:
         for l in reversed(range(d.nL)):
             st = sv["joint"][l]
             dQ = torch.empty(B, T, W, device=dev, dtype=BF16)
-            dK = torch.empty(B, Lp, hd, device=dev, dtype=BF16)
-            dV = torch.empty(B, Lp, hd, device=dev, dtype=BF16)
+            own = "Ko" in st  # several draws on the kernels: compact dK / dV, the pair's rows from 0
+            Lk, k0 = (T, 0) if own else (Lp, P)
+            dK = torch.empty(B, Lk, hd, device=dev, dtype=BF16)
+            dV = torch.empty(B, Lk, hd, device=dev, dtype=BF16)
             dO, dXm = {}, {}
             for g in groups:
                 gs = st["g"][g.name]
@@ -1598,8 +1635,12 @@ class Engine:
                     for g in groups:
                         if g.name in dO:
                             ops.copy_rows(dO[g.name], W, g.T * W, dOall[g.off - P:], W, T * W, B, g.T, W)
-                ops.expert_attn_bwd(Qe, T, 0, Kj, Vj, st["Oall"], st["lse"], dOall, dQ, dK[:, P:], dV[:, P:], P, T, B, nh,
-                                    T, L, scale, 50.0, cnt, P, d.C, P)
+                if own:
+                    ops.expert_attn_bwd_shared(Qe, T, 0, Kj, Vj, st["Ko"], st["Vo"], draws, st["Oall"], st["lse"], dOall,
+                                               dQ, dK, dV, P, T, B, nh, T, L, scale, 50.0, cnt, P, d.C, P)
+                else:
+                    ops.expert_attn_bwd(Qe, T, 0, Kj, Vj, st["Oall"], st["lse"], dOall, dQ, dK[:, P:], dV[:, P:], P, T, B,
+                                        nh, T, L, scale, 50.0, cnt, P, d.C, P)
             else:
                 Pm, tc = st["P"], st["tc"]
                 if dP is None:
@@ -1623,9 +1664,9 @@ class Engine:
                                  batch=B, sA=(T * nh * Lp, 0), sB=(g.T * nh * hd, 0), sC=(Lp * hd, 0), beta=not first)
                         first = False
             for g in groups:
-                self._qkv_backward(g, st["g"][g.name], f"{g.prefix}{l}.", dQ, dK, dV, dX, dXm, pos, B, T, Lp, beta, nh,
-                                   hd, dev, ada.get(g.name), l, qoff=g.off - P)
-            self._chk(f"expert bwd layer {l} (frozen VLM)", dO=dO, dQ=dQ, dK=dK[:, P:P + T], dV=dV[:, P:P + T], dX=dX)
+                self._qkv_backward(g, st["g"][g.name], f"{g.prefix}{l}.", dQ, dK, dV, dX, dXm, pos, B, T, Lk, beta, nh,
+                                   hd, dev, ada.get(g.name), l, qoff=g.off - P, koff=g.off - P + k0)
+            self._chk(f"expert bwd layer {l} (frozen VLM)", dO=dO, dQ=dQ, dK=dK[:, k0:k0 + T], dV=dV[:, k0:k0 + T], dX=dX)
             self._notify("joint", l)
         sv.pop("_jkv_token", None)  # the joint K/V buffers are free for the next forward
         return dX
@@ -1663,7 +1704,7 @@ class Engine:
             ops.copy_rows(dX["proprio"], d.aH, 0, dpe, d.aH, 0, 1, B * d.C, d.aH, scale=sa)
             ops.copy_rows(dX["action"], d.aH, 0, de3, d.aH, 0, 1, B * d.H, d.aH, scale=sa)
 
-    def train_forward(self, ids, pix, cnt, pos, proprios, actions, t, x0, save, prefix_len=None):
+    def train_forward(self, ids, pix, cnt, pos, proprios, actions, t, x0, save, prefix_len=None, draws=1):
         """pizero.py:607-661: returns fp32 loss [1]; ``save`` collects activations.  ``prefix_len`` (int32 [B] on the
         device): rows h < prefix_len[b] are fed clean (psi = bf16(x1), time 1) and carry no loss; None
         launches exactly the kernels of a run without the option.
@@ -1671,19 +1712,29 @@ class Engine:
         With nothing trainable in the VLM (train_vlm: False; PiZero._vlm_needs_grad() false) and the block mask, the
         frozen-VLM pass runs (``vlm_forward_only``): SigLIP, the projector and the vlm mixture forward-only
         on the bf16 inference routes into the joint K/V buffers (no VLM activation and no SigLIP state is saved), then
-        the expert groups alone with their activations saved.  A GeneralMask keeps the full joint pass."""
+        the expert groups alone with their activations saved.  A GeneralMask keeps the full joint pass.
+
+        ``draws`` = S > 1 (flow_samples_per_observation; the frozen-VLM pass only): ids, pix, cnt and
+        pos["vlm"] hold the observations, proprios / actions / t / x0 / prefix_len and the expert positions hold the
+        S pairs of each, pair e = b * S + s.  The prefill runs once, on the observations; the loss is the mean over
+        all pairs -- the loss and gradients of this pass on the batch with every observation repeated S times."""
         d = self.d
         if d.ada and prefix_len is not None:
             raise NotImplementedError(PREFIX_ADAPTIVE_MSG)
         dev = pix.device
-        B = ids.shape[0]
+        nobs = ids.shape[0]
+        B = nobs * draws  # (observation, draw) pairs: the batch of every expert stage
         tied = self.m._tied
         frozen = self.vlm_forward_only and not isinstance(cnt, GeneralMask) and not self.m._vlm_needs_grad()
+        if draws < 1 or (draws > 1 and not frozen):
+            raise ValueError(DRAWS_FROZEN_MSG if draws > 1 else f"draws must be >= 1, got {draws}")
         if frozen:
             sv_v = Xv = None
-            Kall, Vall = self._joint_kv(B, d.Lp, dev, save)
+            Kall, Vall = self._joint_kv(nobs, d.Lp, dev, save)
             with self._bf16_weights():
                 self.prefill(ids, pix, cnt, pos["vlm"], None, None, Kall, Vall, with_proprio=False)
+            if draws > 1:  # the expert attention's prefix counts, per pair
+                cnt = cnt.repeat_interleave(draws).contiguous()
         else:
             sv_v = {}
             img = self.siglip_forward(pix, sv_v)
@@ -1706,7 +1757,7 @@ class Engine:
             save["cond"] = cond
             save["ada"] = {g.name: Ada(self, g, cond) for g in groups if g.name != "vlm"}
         if frozen:
-            X = self._expert_layers_train(groups, X, pos, cnt, B, save, Kall, Vall)
+            X = self._expert_layers_train(groups, X, pos, cnt, B, save, Kall, Vall, draws)
         else:
             X = self._joint_layers_train(groups, X, pos, cnt, B, save)
         ag, Tg = groups[-1].name, groups[-1].T
@@ -1722,7 +1773,7 @@ class Engine:
                       prefix_len=prefix_len)
         save.update(sv_v=sv_v, ids=ids, cnt=cnt, pos=pos, B=B, prop=prop, pe=pe, Xl=Xl, ya=ya, ra=ra,
                     x0=x0, x1=actions, v=v, ag=ag, aoff=aoff, Tg=Tg, groups=groups, prefix_len=prefix_len,
-                    frozen=frozen)
+                    frozen=frozen, draws=draws)
         self._chk("train fwd head (action norm, decoder, flow loss)", embed=Xv, ya=ya, v=v, loss=loss)
         return loss
 
@@ -1755,7 +1806,7 @@ class Engine:
         dX = {g.name: None for g in groups}
         dX[sv["ag"]] = dXl
         if sv.get("frozen"):
-            dX = self._expert_layers_backward(groups, dX, sv["pos"], sv["cnt"], B, sv, beta)
+            dX = self._expert_layers_backward(groups, dX, sv["pos"], sv["cnt"], B, sv, beta, sv.get("draws", 1))
         else:
             dX = self._joint_layers_backward(groups, dX, sv["pos"], sv["cnt"], B, sv, beta)
         if ada:

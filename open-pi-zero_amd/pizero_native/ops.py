@@ -529,9 +529,18 @@ def gemm_qkv_rope(x, W, pos, cs, q_out, k_out, v_out, T, nh, hd, Lq, qoff, Lk, k
     return True
 
 
-def decode_attn(q, Lq, qoff, k, v, o, B, nh, T, nk, scale, cap, cnt, prefix, cond, qtok0, lse=None):
+def _own_kv(name, k_own, v_own, kv_group):
+    """(k_own, v_own, own_bstride, kv_group) of the shared entry points: both own buffers [B, >= nk - prefix, hd] with
+    one batch stride"""
+    if k_own.stride(0) != v_own.stride(0):
+        raise ValueError(f"{name}: k_own and v_own must have the same batch stride")
+    return _p(k_own), _p(v_own), k_own.stride(0), int(kv_group)
+
+
+def decode_attn(q, Lq, qoff, k, v, o, B, nh, T, nk, scale, cap, cnt, prefix, cond, qtok0, lse=None, own=None):
     """Few-query joint attention (denoise): q [B, Lq, nh*hd] rows qoff.., k/v [B, Lk, hd], o [B*T, nh*hd].
-    lse (fp32 [B, T*nh], expert_attn_fwd): the same launches also write each query row's log-sum-exp."""
+    lse (fp32 [B, T*nh], expert_attn_fwd): the same launches also write each query row's log-sum-exp.
+    own (k_own, v_own, kv_group; expert_attn_fwd_shared): key rows >= prefix come from the pair's own buffers."""
     a = DecodeAttnArgs()
     a.q, a.ldq, a.Lq, a.qoff = _p(q), q.shape[-1], Lq, qoff
     a.k, a.v = _p(k), _p(v)
@@ -547,7 +556,9 @@ def decode_attn(q, Lq, qoff, k, v, o, B, nh, T, nk, scale, cap, cnt, prefix, con
     if ws.numel() * 4 < need:
         raise ValueError(f"decode_attn: {B} samples x {nk} keys need {need} B of workspace (> {ws.numel() * 4})")
     a.ws, a.ws_bytes = _p(ws), ws.numel() * 4
-    if lse is not None:
+    if own is not None:
+        call("pz_expert_attn_fwd_shared", C.byref(a), *_own_kv("expert_attn_fwd_shared", *own), _p(lse), _st())
+    elif lse is not None:
         call("pz_expert_attn_fwd", C.byref(a), _p(lse), _st())
     else:
         call("pz_decode_attn", C.byref(a), _st())
@@ -561,8 +572,27 @@ def expert_attn_fwd(q, Lq, qoff, k, v, o, lse, B, nh, T, nk, scale, cap, cnt, pr
     decode_attn(q, Lq, qoff, k, v, o, B, nh, T, nk, scale, cap, cnt, prefix, cond, qtok0, lse=lse)
 
 
+def expert_attn_fwd_shared(q, Lq, qoff, k, v, k_own, v_own, kv_group, o, lse, B, nh, T, nk, scale, cap, cnt, prefix,
+                           cond, qtok0):
+    """pz_expert_attn_fwd_shared (several flow draws per observation): expert_attn_fwd over B (observation,
+    draw) pairs whose key rows < prefix are rows of k / v [B / kv_group, >= prefix, hd] (the observation's VLM keys) and
+    whose key rows >= prefix are rows of k_own / v_own [B, >= nk - prefix, hd] (the pair's own, compact)."""
+    if lse is None:
+        raise ValueError("expert_attn_fwd_shared: lse is required")
+    decode_attn(q, Lq, qoff, k, v, o, B, nh, T, nk, scale, cap, cnt, prefix, cond, qtok0, lse=lse,
+                own=(k_own, v_own, kv_group))
+
+
+def expert_attn_bwd_shared(q, Lq, qoff, k, v, k_own, v_own, kv_group, o, lse, dO, dq, dk, dv, key0, nkeys, B, nh, T, nk,
+                           scale, cap, cnt, prefix, cond, qtok0, ws=None):
+    """pz_expert_attn_bwd_shared: expert_attn_bwd with expert_attn_fwd_shared's key addressing; dq / dk / dv per pair,
+    the shared k / v only read."""
+    expert_attn_bwd(q, Lq, qoff, k, v, o, lse, dO, dq, dk, dv, key0, nkeys, B, nh, T, nk, scale, cap, cnt, prefix, cond,
+                    qtok0, ws=ws, own=(k_own, v_own, kv_group))
+
+
 def expert_attn_bwd(q, Lq, qoff, k, v, o, lse, dO, dq, dk, dv, key0, nkeys, B, nh, T, nk, scale, cap, cnt, prefix, cond,
-                    qtok0, ws=None):
+                    qtok0, ws=None, own=None):
     """pz_expert_attn_bwd: dq (addressed like q) and dk / dv [B, >= nkeys, hd] -- the rows of keys
     [key0, key0 + nkeys), e.g. views dK[:, key0:] of [B, Lp, hd] buffers, whose other rows stay untouched -- from the
     forward's q / k / v / o / lse and dO [B*T, nh*hd].  ws: fp32 scratch (default: allocated here)."""
@@ -582,7 +612,10 @@ def expert_attn_bwd(q, Lq, qoff, k, v, o, lse, dO, dq, dk, dv, key0, nkeys, B, n
     if ws is None:
         ws = torch.empty(max(need // 4, 4), device=q.device, dtype=torch.float32)
     a.ws, a.ws_bytes = _p(ws), ws.numel() * 4
-    call("pz_expert_attn_bwd", C.byref(a), _st())
+    if own is not None:
+        call("pz_expert_attn_bwd_shared", C.byref(a), *_own_kv("expert_attn_bwd_shared", *own), _st())
+    else:
+        call("pz_expert_attn_bwd", C.byref(a), _st())
 
 
 def attn_softmax(S, lds, P, ldp, R, N, scale, cap=0.0, tcap=None, mask_mode=0, rows_per_batch=1, heads=1,

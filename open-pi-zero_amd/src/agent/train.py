@@ -189,6 +189,21 @@ class TrainAgent:
             if self.main_rank and not model._vlm_needs_grad():
                 log.info("train_vlm False: frozen-VLM pass active (VLM forward-only, expert-only backward%s)",
                          "; the frozen VLM region is left out of the all-reduce" if self.multi_gpu else "")
+        # several flow draws per observation: S pairs (t, x0) per sample of a micro-batch share its one
+        # forward-only VLM prefill.  1 (default): the step as it always was
+        fs = cfg_get(cfg, "flow_samples_per_observation", 1)
+        self.flow_samples = 1 if fs is None else int(fs)
+        if self.flow_samples < 1:
+            raise ValueError(f"flow_samples_per_observation must be >= 1, got {self.flow_samples}")
+        if self.flow_samples > 1:
+            if self.train_vlm or model._vlm_needs_grad():
+                from pizero_native.engine import DRAWS_FROZEN_MSG
+
+                raise ValueError(DRAWS_FROZEN_MSG + f" (got train_vlm: {self.train_vlm}, lora: {self.lora})")
+            if self.main_rank:
+                log.info("flow_samples_per_observation %d: every observation trains on %d flow draws (t, x0) that share "
+                         "its one VLM prefill; %d pairs per micro-batch", self.flow_samples, self.flow_samples,
+                         per_dev * self.flow_samples)
         self.flow_sampling = cfg_get(cfg, "flow_sampling", "beta")
         self.flow_t_max = 1 - float(cfg_get(cfg, "flow_sig_min", 0.001))
         self.flow_beta_dist = torch.distributions.Beta(float(cfg_get(cfg, "flow_alpha", 1.5)),
@@ -287,7 +302,9 @@ class TrainAgent:
         else:
             inputs["causal_mask"] = mask
         if sample_fm_time:
-            inputs["t"] = self.sample_fm_time(len(batch["input_ids"])).to(dev, **nb).to(self.dtype)
+            bsz, S = len(batch["input_ids"]), self.flow_samples
+            t = self.sample_fm_time(bsz * S)
+            inputs["t"] = (t.view(bsz, S) if S > 1 else t).to(dev, **nb).to(self.dtype)
             pl = self._prefix_len(batch)
             if pl is not None:
                 inputs["prefix_len"] = pl

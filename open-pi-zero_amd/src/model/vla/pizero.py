@@ -75,6 +75,29 @@ def adaln_slots(prefix: str, n_layers: int, mode: str):
     return {"w": w, "b": b, "slot": slot}
 
 
+def flow_draws(B, H, A, t_shape, noise_shape=None, prefix_len_shape=None):
+    """Number of flow draws per observation S (``flow_samples_per_observation``) that the shapes of
+    PiZero.forward's ``t`` ([B] -> 1, [B, S] -> S), ``noise`` ([B, H, A] or [B, S, H, A]) and ``prefix_len`` ([B],
+    broadcast over the draws, or [B, S]) ask for, for B observations; shapes that disagree are refused.  Shapes only:
+    runs without a device."""
+    key = "flow_samples_per_observation"
+    t_shape = tuple(t_shape)
+    if len(t_shape) not in (1, 2) or t_shape[0] != B or (len(t_shape) == 2 and t_shape[1] < 1):
+        raise ValueError(f"t must be [B] or [B, S] ({key}: S >= 1 draws per observation) with B = {B}, got "
+                         f"{list(t_shape)}")
+    two = len(t_shape) == 2
+    S = t_shape[1] if two else 1
+    if noise_shape is not None:
+        want = (B, S, H, A) if two else (B, H, A)
+        if tuple(noise_shape) != want:
+            raise ValueError(f"{key}: noise must be {list(want)} for t of shape {list(t_shape)} (one x0 per draw), got "
+                             f"{list(noise_shape)}")
+    if prefix_len_shape is not None and len(tuple(prefix_len_shape)) == 2 and tuple(prefix_len_shape) != (B, S):
+        raise ValueError(f"{key}: prefix_len must be [B] (shared by an observation's draws) or [B, S] = [{B}, {S}], got "
+                         f"{list(prefix_len_shape)}")
+    return S
+
+
 class _PiZeroLoss(torch.autograd.Function):
     """Whole-model autograd node: native forward, native backward into the grad arena."""
 
@@ -723,28 +746,51 @@ class PiZero(nn.Module, NoSyncBase):
                 prefix_len: Optional[torch.Tensor] = None):
         """Flow-matching loss (pizero.py:607-661); ``noise`` = x0 (default torch.randn_like).  ``prefix_len`` (ints
         [B]): the first prefix_len[b] actions of sample b are a committed prefix -- fed clean with flow
-        time 1, given no loss, attended to by the rest.  None: today's loss, with today's kernels."""
+        time 1, given no loss, attended to by the rest.  None: today's loss, with today's kernels.
+
+        Several flow draws per observation (``flow_samples_per_observation``; frozen-VLM pass only): ``t``
+        [B, S] with ``noise`` [B, S, H, A] (default randn) trains on the B * S pairs (observation b, draw s), each with
+        its own t and x0, all of b sharing its images, prompt, proprio and actions; the VLM prefill runs once per
+        observation.  ``prefix_len`` is then [B] (shared by the draws) or [B, S].  The loss is the mean over all pairs:
+        the loss of the batch with every observation repeated S times.  ``t`` [B] is today's step."""
         dev = self._dev()
         cdt = self._arena.data.dtype
         if cdt != torch.bfloat16:
             raise RuntimeError("the native path computes in bf16: call model.to(torch.bfloat16)")
+        B, H, A = actions.shape
+        two = t.dim() == 2  # [B, S]: pairs, even for S == 1
+        S = flow_draws(B, H, A, t.shape, None if noise is None else noise.shape,
+                       prefix_len.shape if isinstance(prefix_len, torch.Tensor) else None)
         x1 = actions.to(dev, torch.float32).contiguous()
-        x0 = (torch.randn_like(x1) if noise is None else noise.to(dev, torch.float32)).contiguous()
         cm = causal_mask.to(dev)
+        cnt = self._mask_spec([cm], [torch.arange(cm.shape[2], device=dev)])
+        if S > 1:
+            from pizero_native.engine import DRAWS_FROZEN_MSG, GeneralMask
+
+            if self._vlm_needs_grad() or isinstance(cnt, GeneralMask):
+                raise ValueError(DRAWS_FROZEN_MSG)
+        rep = (lambda x: x.repeat_interleave(S, dim=0)) if S > 1 else (lambda x: x)  # observation -> its S pairs
+        x1 = rep(x1)
+        x0 = (torch.randn_like(x1) if noise is None else noise.to(dev, torch.float32).reshape(B * S, H, A)).contiguous()
         tied = self._tied
         pos = {"vlm": vlm_position_ids.to(dev, torch.int64).contiguous()}
         if tied:
-            pos["expert"] = self._cat_pos(proprio_position_ids, action_position_ids)
+            pos["expert"] = rep(self._cat_pos(proprio_position_ids, action_position_ids))
         else:
-            pos["proprio"] = proprio_position_ids.to(dev, torch.int64).contiguous()
-            pos["action"] = action_position_ids.to(dev, torch.int64).contiguous()
+            pos["proprio"] = rep(proprio_position_ids.to(dev, torch.int64).contiguous())
+            pos["action"] = rep(action_position_ids.to(dev, torch.int64).contiguous())
         batch = dict(ids=input_ids.to(dev, torch.int64).contiguous(),
-                     pix=pixel_values.to(dev, torch.bfloat16).contiguous(),
-                     cnt=self._mask_spec([cm], [torch.arange(cm.shape[2], device=dev)]), pos=pos,
-                     proprios=proprios.to(dev, torch.float32).contiguous(), actions=x1,
-                     t=t.to(dev, torch.float32).contiguous(), x0=x0)
+                     pix=pixel_values.to(dev, torch.bfloat16).contiguous(), cnt=cnt, pos=pos,
+                     proprios=rep(proprios.to(dev, torch.float32).contiguous()), actions=x1,
+                     t=t.to(dev, torch.float32).reshape(B * S).contiguous(), x0=x0)
         if prefix_len is not None:
-            batch["prefix_len"] = self._prefix_len(prefix_len, x1.shape[0])
+            pl = torch.as_tensor(prefix_len)
+            if two and pl.dim() == 2:
+                batch["prefix_len"] = self._prefix_len(pl.reshape(B * S), B * S)
+            else:
+                batch["prefix_len"] = rep(self._prefix_len(pl, B))
+        if S > 1:
+            batch["draws"] = S
         anchor = next((self._param(n) for n in self._trainable_names()), None)
         if anchor is not None and torch.is_grad_enabled():
             self._check_ddp_wrapper()
